@@ -13,8 +13,16 @@ Data: synthetic uint8 224x224 images resident on the GPU, random-init weights
 (no datasets/checkpoints offline).  Every timed step is a full train step: forward, backward,
 RCCL gradient all-reduce, optimizer update.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (driver launches N>1 like this)
+
+A plain run sets up, warms up, times the K steps and prints the JSON result line.
+``--dump-outputs DIR`` then writes what the last timed step returned and updated (its metrics, and
+a fixed seeded sample of the fp32 master weights and of the flat gradient) as ``DIR/<name>.npy``;
+the inputs are seeded, so two builds can be compared output for output.  ``--full`` adds what the
+headline figure does not need: the fp64 weight checksum and its spread over the data-parallel
+replicas, and at N > 1 the traced step and the timed collectives (``collective_sweep``,
+``dp_ready_spans``) that tools/dp_exposure_model.py --sweep reads.
 
 Secondary BASELINE.json configs (not the headline): ``--task finetune`` = ViT-B/16 end-to-end
 finetune with the config/ft.sh recipe (AdamW + LLRD 0.75, Mixup 0.8 / CutMix 1.0, label
@@ -74,6 +82,11 @@ def main():
     ap.add_argument("--cpu", action="store_true",
                     help="tests only: run the same flow on the CPU (gloo when distributed, fp32 PyTorch path)")
     ap.add_argument("--image-size", type=int, default=224, help=argparse.SUPPRESS)  # tests: smaller images
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned and updated as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and measurements beside the headline figure: weight checksum and its "
+                         "spread over the replicas, multi-GPU collective calibration")
     args = ap.parse_args()
     if args.task != "pretrain":
         return bench_classifier(args)
@@ -171,17 +184,22 @@ def main():
     elapsed = pdist.all_reduce_max_scalar(elapsed, dev)
     final_loss = float(m["loss"].item())
     comm_ms = trainer.comm_ms()
-    # multi-GPU self-calibration, outside the timed region: one traced step (when each bucket's
-    # gradient became final, on the GPU clock) and one timed collective per distinct bucket size
-    # of the real plan -- the inputs of tools/dp_exposure_model.py (--sweep reads this JSON line)
-    calib = trace_and_calibrate(reducer, step, dev) if (reducer is not None and world > 1) else None
-    if reducer is not None and reducer.shard:
-        opt.gather_state()  # ZeRO-1: the sharded fp32 master (and moments) made whole for the checksum
-    # data-parallel replicas must hold identical weights after the timed steps (outside the timed
-    # region): spread of a weight checksum over the ranks, 0.0 when in sync
-    spread = pdist.all_reduce_max_scalar(float(store.master.double().abs().sum()), dev) - \
-        -pdist.all_reduce_max_scalar(-float(store.master.double().abs().sum()), dev) if world > 1 else 0.0
-    weight_checksum = float(store.master.double().abs().sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, store, opt, reducer, info.is_main)
+    calib, extra = None, {}
+    if args.full:
+        # multi-GPU self-calibration, outside the timed region: one traced step (when each bucket's
+        # gradient became final, on the GPU clock) and one timed collective per distinct bucket size
+        # of the real plan -- the inputs of tools/dp_exposure_model.py (--sweep reads this JSON line)
+        calib = trace_and_calibrate(reducer, step, dev) if (reducer is not None and world > 1) else None
+        if reducer is not None and reducer.shard:
+            opt.gather_state()  # ZeRO-1: the sharded fp32 master (and moments) made whole for the checksum
+        # data-parallel replicas must hold identical weights after the timed steps (outside the timed
+        # region): spread of a weight checksum over the ranks, 0.0 when in sync
+        spread = pdist.all_reduce_max_scalar(float(store.master.double().abs().sum()), dev) - \
+            -pdist.all_reduce_max_scalar(-float(store.master.double().abs().sum()), dev) if world > 1 else 0.0
+        extra = {"replica_weight_checksum_spread": spread,
+                 "weight_checksum": float(store.master.double().abs().sum())}
 
     if args.profile_steps > 0 and info.is_main:
         from torch.profiler import ProfilerActivity, profile
@@ -218,7 +236,7 @@ def main():
             "exposed_comm_ms_last_step": None if comm_ms is None else round(comm_ms, 3),
             # peak HBM held by PyTorch's allocator on this rank (torch.cuda.max_memory_allocated)
             "peak_hbm_gb": peak_gb,
-            "replica_weight_checksum_spread": spread, "weight_checksum": weight_checksum,
+            **extra,
             "reducer": reducer.stats() if reducer is not None else None,
             **(calib or {}),
             "dtype": "fp32" if args.cpu else "bf16",
@@ -240,6 +258,40 @@ def main():
         }
         print(json.dumps(out), flush=True)
     pdist.cleanup()
+
+
+def _sample(t: torch.Tensor, limit: int = 4 << 20):
+    """``t`` flattened as a float32 numpy array; above ``limit`` elements a fixed seeded sample of
+    ``limit`` of them (sorted indices, the same from run to run)."""
+    t = t.detach().reshape(-1)
+    if t.numel() > limit:
+        idx = torch.randint(0, t.numel(), (limit,), generator=torch.Generator().manual_seed(20240607))
+        t = t[idx.sort().values.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, metrics, store, opt, reducer, is_main) -> None:
+    """What the last timed step gave its caller, as ``<path>/<name>.npy`` (float32, <= 16 MiB each):
+    every entry of the returned metrics, and the two flat buffers the step updates in place -- the
+    fp32 master weights and the gradient -- sampled at fixed seeded indices when they are larger.
+    Rank 0 writes.  ZeRO-1 (``--shard-optimizer``) at N > 1: the state is gathered first, but a
+    reduce-scatter leaves the reduced gradient only in each rank's own shard, so ``grad.npy`` is
+    the reduced gradient there and rank 0's local one elsewhere."""
+    import os
+
+    import numpy as np
+    if reducer is not None and reducer.shard:
+        # COLLECTIVE (every rank): ZeRO-1 state made whole before it is read (--full gathers again
+        # for its checksum, after the calibration step has updated the shards once more)
+        opt.gather_state()
+    if not is_main:
+        return
+    os.makedirs(path, exist_ok=True)
+    for k, v in metrics.items():
+        a = _sample(v) if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(path, f"metric_{k}.npy"), a)
+    np.save(os.path.join(path, "master_weights.npy"), _sample(store.master))
+    np.save(os.path.join(path, "grad.npy"), _sample(store.grad))
 
 
 def trace_and_calibrate(reducer, step, dev) -> dict:
@@ -356,6 +408,8 @@ def bench_classifier(args):
     pdist.barrier()
     torch.cuda.synchronize()
     elapsed = pdist.all_reduce_max_scalar(time.perf_counter() - t0, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, model.store, opt, reducer, info.is_main)
     value = gb * args.steps / elapsed
     fwd = finetune_fwd_flops_per_image(model.cfg)
     util = mfu(value, fwd, world) if args.task == "finetune" else mfu(value, fwd, world) / 3.0

@@ -1,4 +1,4 @@
-"""Collective timing helpers shared by ``tools/allreduce_bench.py`` (node sweeps) and ``bench.py``
+"""Collective timing helpers shared by ``tools/allreduce_bench.py`` (node sweeps) and ``bench.py --full``
 (self-calibration of the first multi-GPU run: the real bucket sizes of the step's reducer plan,
 timed on the real process group after the timed steps).
 

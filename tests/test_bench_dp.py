@@ -26,7 +26,7 @@ def test_bench_two_ranks_cpu(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu", "--model", "vit_tiny_patch16",
-           "--batch-per-gpu", "4", "--image-size", "64", "--bucket-mb", "0.5"] + extra
+           "--batch-per-gpu", "4", "--image-size", "64", "--bucket-mb", "0.5", "--full"] + extra
     env = dict(os.environ, OMP_NUM_THREADS="2")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd="/tmp", env=env)
     assert r.returncode == 0, r.stderr[-3000:]

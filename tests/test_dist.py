@@ -165,7 +165,7 @@ def _driver_worker(rank, world, port, outdir):
         "--layers", "1", "--dim", "32", "--heads", "2", "--labels", "0", "--image-size", "32", "--patch-size", "8",
         "--dec-layers", "1", "--dec-dim", "16", "--dec-heads", "2", "--training-steps", "4", "--warmup-steps", "1",
         "--log-interval", "2", "--eval-interval", "4", "--output-dir", outdir, "--name", "dd", "--grad-accum", "2",
-        "--init-seed", "0", "--log-file-only"])
+        "--init-seed", "0", "--log-file-only", "--device", "cpu"])  # gloo ranks: not one GPU per rank
     res = main(args)
     if rank == 0:
         torch.save(res, os.path.join(outdir, "res.pt"))

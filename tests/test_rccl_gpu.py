@@ -27,7 +27,7 @@ def _port():
 
 
 def _run(args, torchrun: bool, force: bool, timeout: int = 300):
-    bench = [os.path.join(ROOT, "bench.py")] + args
+    bench = [os.path.join(ROOT, "bench.py"), "--full"] + args  # --full: the weight checksum compared below
     if torchrun:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                "--master-addr", "127.0.0.1", "--master-port", str(_port())] + bench

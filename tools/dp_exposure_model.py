@@ -41,8 +41,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def load_sweep(path):
-    """``collective_sweep`` rows from a tools/allreduce_bench.py --json file, a bench.py JSON line
-    (the multi-GPU run's self-calibration: one row per bucket size of the real plan), or a driver
+    """``collective_sweep`` rows from a tools/allreduce_bench.py --json file, a bench.py --full JSON
+    line (the multi-GPU run's self-calibration: one row per bucket size of the real plan), or a driver
     record holding that line under "parsed"."""
     d = json.load(open(path))
     for k in ("parsed", "result"):
