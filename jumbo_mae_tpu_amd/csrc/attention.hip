@@ -1284,32 +1284,76 @@ int dispatch_sp(bool fwd, const uint16_t* qkv, const uint16_t* o, const uint16_t
 //                         sweeps 64-query tiles: dV^T += dO^T P, dK^T += Q^T dS.
 // Every output element has one writer: no atomics, deterministic.  Grid x = (b, h) major, tile
 // minor, so the WGs sharing one (b, h)'s K / V (or Q / dO) rows are dispatched together.
+//
+// Head dims 80 / 96 / 128 run on these kernels at every S (jm_attn_tiled).  The contractions over
+// d (QK^T, dO V^T) take hd rounded up to 32 columns, the depth of one MFMA: at hd = 80 the last
+// step's upper 16 columns are a pad that is zero on BOTH operands -- zero-filled once in the LDS
+// tiles (tile_zero_pad; tile_store never writes there) and never loaded into the register
+// fragments (frag_in) -- because the columns behind a head in memory belong to the next head, the
+// next row or nobody.  The products over keys / queries (DT = hd / 16 output tiles) need no pad.
 constexpr int LT = 64;
 
+// columns of the d contraction (hd rounded up to the MFMA depth) and the LDS row stride
+template <int HD>
+constexpr int lkp() {
+  return (HD + 31) / 32 * 32;
+}
+template <int HD>
+constexpr int lks() {
+  return lkp<HD>() + 8;
+}
+
+// whether lane group g's 8 columns of contraction step kk lie inside the head
+template <int HD>
+JM_DEVICE bool frag_in(int kk, int g) {
+  return HD % 32 == 0 || 32 * kk + 8 * g < HD;
+}
+
 // a 64 x HD bf16 tile moves HBM -> registers (issued one tile ahead, so its latency hides behind
-// the current tile's MFMA work) -> LDS (row stride HD + 8); rows past S are zero
+// the current tile's MFMA work) -> LDS (row stride lks); rows past S are zero.  The tile's
+// 64 * HD / 8 16-byte chunks are dealt over the 256 threads; at hd = 80 (640 chunks) the third
+// pass is half empty and guarded.
 template <int HD>
 struct TileRegs {
-  uint4 v[HD / 32];
+  uint4 v[lkp<HD>() / 32];
 };
+
+template <int HD>
+JM_DEVICE bool tile_chunk(int i) {
+  return HD % 32 == 0 || i < LT * (HD / 8);
+}
 
 template <int HD>
 JM_DEVICE void tile_fetch(TileRegs<HD>& t, const uint16_t* src, long rs, int r0, int S) {
   constexpr int CPR = HD / 8;
 #pragma unroll
-  for (int j = 0; j < HD / 32; ++j) {
+  for (int j = 0; j < lkp<HD>() / 32; ++j) {
     const int i = threadIdx.x + 256 * j, r = i / CPR, c = (i % CPR) * 8;
-    t.v[j] = r0 + r < S ? *reinterpret_cast<const uint4*>(src + (long)(r0 + r) * rs + c) : make_uint4(0, 0, 0, 0);
+    t.v[j] = tile_chunk<HD>(i) && r0 + r < S ? *reinterpret_cast<const uint4*>(src + (long)(r0 + r) * rs + c)
+                                             : make_uint4(0, 0, 0, 0);
   }
 }
 
 template <int HD>
 JM_DEVICE void tile_store(uint16_t* dst, const TileRegs<HD>& t) {
-  constexpr int CPR = HD / 8, KS = HD + 8;
+  constexpr int CPR = HD / 8, KS = lks<HD>();
 #pragma unroll
-  for (int j = 0; j < HD / 32; ++j) {
+  for (int j = 0; j < lkp<HD>() / 32; ++j) {
     const int i = threadIdx.x + 256 * j, r = i / CPR, c = (i % CPR) * 8;
-    *reinterpret_cast<uint4*>(dst + r * KS + c) = t.v[j];
+    if (tile_chunk<HD>(i)) *reinterpret_cast<uint4*>(dst + r * KS + c) = t.v[j];
+  }
+}
+
+// zero columns [HD, lkp) of both LDS tiles, once, before the tile loop (its first barrier orders
+// these stores before any read)
+template <int HD>
+JM_DEVICE void tile_zero_pad(uint16_t* a, uint16_t* b) {
+  if constexpr (HD % 32 != 0) {
+    constexpr int PC = (lkp<HD>() - HD) / 8;  // pad chunks per row
+    for (int i = threadIdx.x; i < 2 * LT * PC; i += 256) {
+      const int r = (i / PC) % LT, c = HD + (i % PC) * 8;
+      *reinterpret_cast<uint4*>((i < LT * PC ? a : b) + r * lks<HD>() + c) = make_uint4(0, 0, 0, 0);
+    }
   }
 }
 
@@ -1317,7 +1361,7 @@ JM_DEVICE void tile_store(uint16_t* dst, const TileRegs<HD>& t) {
 // like the packed P^T / dS^T fragments (rows 4g..4g+3, then 16+4g..16+4g+3)
 template <int HD>
 JM_DEVICE bf16x8_t tr_frag(const uint16_t* t, int s, int dt, int l16, int g) {
-  constexpr int KS = HD + 8;
+  constexpr int KS = lks<HD>();
   const uint16_t* p = t + (32 * s + 4 * g + (l16 >> 2)) * KS + dt * 16 + 4 * (l16 & 3);
   return cat44(tr4(p), tr4(p + 16 * KS));
 }
@@ -1326,7 +1370,7 @@ template <int HD>
 __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* __restrict__ qkv,
                                                             uint16_t* __restrict__ o, float* __restrict__ lse,
                                                             int S, int H, float scale) {
-  constexpr int KS = HD + 8, KK = HD / 32, DT = HD / 16;
+  constexpr int KS = lks<HD>(), KK = lkp<HD>() / 32, DT = HD / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[LT * KS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[LT * KS];
   const int nq = (S + LT - 1) / LT;
@@ -1344,13 +1388,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* _
 #pragma unroll
   for (int kk = 0; kk < KK; ++kk) {
     s16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-    qf[kk] = q < S ? ld8(base + (long)q * ts + h * HD + 32 * kk + 8 * g) : __builtin_bit_cast(bf16x8_t, z);
+    qf[kk] = q < S && frag_in<HD>(kk, g) ? ld8(base + (long)q * ts + h * HD + 32 * kk + 8 * g)
+                                         : __builtin_bit_cast(bf16x8_t, z);
   }
   f32x4_t oacc[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) oacc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
 
+  tile_zero_pad<HD>(Ks, Vs);
   TileRegs<HD> kr, vr;
   tile_fetch<HD>(kr, Kg, ts, 0, S);
   tile_fetch<HD>(vr, Vg, ts, 0, S);
@@ -1424,7 +1470,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
                                                           const float* __restrict__ lse,
                                                           uint16_t* __restrict__ dqkv, float* __restrict__ delta,
                                                           int S, int H, float scale) {
-  constexpr int KS = HD + 8, KK = HD / 32, DT = HD / 16;
+  constexpr int KS = lks<HD>(), KK = lkp<HD>() / 32, DT = HD / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[LT * KS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[LT * KS];
   const int nq = (S + LT - 1) / LT;
@@ -1444,7 +1490,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   for (int kk = 0; kk < KK; ++kk) {
     s16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
     qf[kk] = df[kk] = __builtin_bit_cast(bf16x8_t, z);
-    if (q < S) {
+    if (q < S && frag_in<HD>(kk, g)) {
       const long orow = ((long)b * S + q) * H * HD + h * HD + 32 * kk + 8 * g;
       qf[kk] = ld8(base + (long)q * ts + h * HD + 32 * kk + 8 * g);
       df[kk] = ld8(dO + orow);
@@ -1463,6 +1509,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   f32x4_t dq[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  tile_zero_pad<HD>(Ks, Vs);
   TileRegs<HD> kr, vr;
   tile_fetch<HD>(kr, Kg, ts, 0, S);
   tile_fetch<HD>(vr, Vg, ts, 0, S);
@@ -1515,7 +1562,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
                                                            const float* __restrict__ lse,
                                                            const float* __restrict__ delta,
                                                            uint16_t* __restrict__ dqkv, int S, int H, float scale) {
-  constexpr int KS = HD + 8, KK = HD / 32, DT = HD / 16;
+  constexpr int KS = lks<HD>(), KK = lkp<HD>() / 32, DT = HD / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Qs[LT * KS];
   __shared__ __attribute__((aligned(16))) uint16_t Ds[LT * KS];
   __shared__ float Ls[LT], Dl[LT];
@@ -1537,7 +1584,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
   for (int kk = 0; kk < KK; ++kk) {
     s16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
     kf[kk] = vf[kk] = __builtin_bit_cast(bf16x8_t, z);
-    if (kv) {
+    if (kv && frag_in<HD>(kk, g)) {
       kf[kk] = ld8(base + (long)key * ts + (H + h) * HD + 32 * kk + 8 * g);
       vf[kk] = ld8(base + (long)key * ts + (2 * H + h) * HD + 32 * kk + 8 * g);
     }
@@ -1546,6 +1593,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dk[dt] = dv[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
+  tile_zero_pad<HD>(Qs, Ds);
   TileRegs<HD> qr, dr;
   float lr = INFINITY, dlr = 0.f;
   auto fetch = [&](int r0) {
@@ -1638,6 +1686,24 @@ int run_long_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, con
 constexpr int ATTN_MAX_SEQ = 224;
 int jm_attn_max_seq() { return ATTN_MAX_SEQ; }
 
+// head dims with HIP kernels: 32 / 64 on both kernel families, 80 / 96 / 128 tile-streamed only
+static const int ATTN_HEAD_DIMS[] = {32, 64, 80, 96, 128};
+int jm_attn_head_dims(const int** dims) {
+  *dims = ATTN_HEAD_DIMS;
+  return (int)(sizeof(ATTN_HEAD_DIMS) / sizeof(int));
+}
+static bool whole_seq_hd(int hd) { return hd == 32 || hd == 64; }
+static bool tiled_only_hd(int hd) { return hd == 80 || hd == 96 || hd == 128; }
+
+// 1: (S, hd) runs on the tile-streamed kernels -- jm_attn_fwd takes them itself, the backward is
+// jm_attn_bwd_long (delta workspace, no dropout); 0: on the whole-sequence kernels (jm_attn_bwd)
+// or unsupported
+int jm_attn_tiled(int S, int hd) { return tiled_only_hd(hd) || (whole_seq_hd(hd) && S > ATTN_MAX_SEQ); }
+
+// 1 exactly where the backward can add the QKV bias gradient (jm_attn_bwd's dbias_part): the
+// whole-sequence kernels.  Elsewhere the caller takes colsum(dqkv).
+int jm_attn_fused_bias(int S, int hd) { return whole_seq_hd(hd) && S <= ATTN_MAX_SEQ; }
+
 // rows of the dbias_part workspace that jm_attn_bwd writes: the bwd2 kernel folds BWD2_PPW batch
 // elements into one row, every other backward writes one row per batch element.
 int jm_attn_bwd_part_rows(int B, int S, int hd) {
@@ -1651,10 +1717,13 @@ int jm_attn_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int 
                 uint32_t dthr, float dscale, hipStream_t st) {
   const float scale = 1.f / sqrtf((float)hd);
   const AttnDrop dr{dseed, dthr, dscale};
-  if (S > jm_attn_max_seq()) {
+  if (jm_attn_tiled(S, hd)) {
     if (dseed != nullptr) return -5;
     if (hd == 32) return run_long_fwd<32>(qkv, o, lse, B, S, H, scale, st);
     if (hd == 64) return run_long_fwd<64>(qkv, o, lse, B, S, H, scale, st);
+    if (hd == 80) return run_long_fwd<80>(qkv, o, lse, B, S, H, scale, st);
+    if (hd == 96) return run_long_fwd<96>(qkv, o, lse, B, S, H, scale, st);
+    if (hd == 128) return run_long_fwd<128>(qkv, o, lse, B, S, H, scale, st);
     return -1;
   }
   if (hd == 32) return dispatch_sp<32>(true, qkv, nullptr, nullptr, nullptr, o, lse, B, S, H, scale, dr, st);
@@ -1662,24 +1731,30 @@ int jm_attn_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int 
   return -1;
 }
 
-// dbias_part: optional [B][3*H*hd] fp32 per-sample column sums of dqkv (see attn_bwd_kernel)
+// dbias_part: optional [B][3*H*hd] fp32 per-sample column sums of dqkv (see attn_bwd_kernel).
+// Whole-sequence kernels only: -2 where jm_attn_tiled(S, hd) (the head dims 80 / 96 / 128 at any
+// S included), whose backward needs jm_attn_bwd_long's workspace.
 int jm_attn_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv, int B,
                 int S, int H, int hd, float* dbias_part, const int64_t* dseed, uint32_t dthr, float dscale,
                 hipStream_t st) {
   const float scale = 1.f / sqrtf((float)hd);
   const AttnDrop dr{dseed, dthr, dscale};
+  if (jm_attn_tiled(S, hd)) return -2;
   if (hd == 32) return dispatch_sp<32>(false, qkv, o, dO, lse, dqkv, dbias_part, B, S, H, scale, dr, st);
   if (hd == 64) return dispatch_sp<64>(false, qkv, o, dO, lse, dqkv, dbias_part, B, S, H, scale, dr, st);
   return -1;
 }
 
-// S > jm_attn_max_seq(): tile-streamed backward; delta = fp32 [B][H][S] workspace.  No fused
+// jm_attn_tiled(S, hd): tile-streamed backward; delta = fp32 [B][H][S] workspace.  No fused
 // bias colsum on this path (the caller takes colsum(dqkv)).
 int jm_attn_bwd_long(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv,
                      float* delta, int B, int S, int H, int hd, hipStream_t st) {
   const float scale = 1.f / sqrtf((float)hd);
   if (hd == 32) return run_long_bwd<32>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
   if (hd == 64) return run_long_bwd<64>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
+  if (hd == 80) return run_long_bwd<80>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
+  if (hd == 96) return run_long_bwd<96>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
+  if (hd == 128) return run_long_bwd<128>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
   return -1;
 }
 

@@ -736,14 +736,21 @@ def residual_bwd(dout3: torch.Tensor, y2: torch.Tensor | None, hs: Handle | None
 
 # ------------------------------------------------------------------------------ attention
 def _attn_hip(qkv: torch.Tensor, heads: int) -> bool:
-    """HIP attention covers head dims 32 / 64 at any length: the fused whole-sequence-in-LDS
-    kernels up to S = attn_max_seq() (224: every flagship shape), tile-streamed online-softmax
-    kernels beyond (e.g. finetuning at 448 px, S = 787).  Other head dims take
-    the PyTorch composition below (fp32 softmax, same numerics)."""
+    """HIP attention covers the head dims of ``ext.attn_head_dims()`` at any length.  32 / 64: the
+    fused whole-sequence-in-LDS kernels up to S = attn_max_seq() (224: every flagship shape),
+    tile-streamed online-softmax kernels beyond (e.g. finetuning at 448 px, S = 787; SURVEY.md
+    §5.7).  80 / 96 / 128 (ViT-H/14: 1280 / 16 = 80): the tile-streamed kernels at every S.  Other
+    head dims take the PyTorch composition below (fp32 softmax, same numerics)."""
     if not hip(qkv):
         return False
     hd = qkv.shape[2] // 3 // heads
-    return hd in (32, 64)
+    return hd in _ext.load().attn_head_dims()
+
+
+def _attn_drop_hip(S: int, hd: int) -> bool:
+    """Attention-probability dropout is fused into the whole-sequence kernels only -- the (S, hd)
+    where the backward also fuses the bias gradient; elsewhere dropout takes the composition."""
+    return _ext.load().attn_fused_bias(S, hd)
 
 
 def _drop_mask(drop, B: int, heads: int, S: int, device):
@@ -758,12 +765,13 @@ def _drop_mask(drop, B: int, heads: int, S: int, device):
 
 def attn_fwd(qkv: torch.Tensor, heads: int, drop=None):
     """qkv [B, S, 3*D] -> (o [B, S, D], lse [B, H, S]).  ``drop`` = (seed int64 [1] tensor, rate):
-    dropout on the attention probabilities (reference modeling.py:137), fused into the kernels up
-    to S = attn_max_seq(); lse is that of the undropped softmax."""
+    dropout on the attention probabilities (reference modeling.py:137), fused into the
+    whole-sequence kernels (head dims 32 / 64 up to S = attn_max_seq()); lse is that of the
+    undropped softmax."""
     B, S, three_d = qkv.shape
     D = three_d // 3
     hd = D // heads
-    if _attn_hip(qkv, heads) and (drop is None or S <= _ext.load().attn_max_seq()):
+    if _attn_hip(qkv, heads) and (drop is None or _attn_drop_hip(S, hd)):
         if drop is None:
             return _ext.load().attn_fwd(qkv, heads)
         return _ext.load().attn_fwd(qkv, heads, drop[0], drop[1])
@@ -785,9 +793,9 @@ def attn_bwd(do: torch.Tensor, qkv: torch.Tensor, o: torch.Tensor, lse: torch.Te
     D = three_d // 3
     hd = D // heads
     do = do.contiguous().view(B, S, D)
-    if _attn_hip(qkv, heads) and (drop is None or S <= _ext.load().attn_max_seq()):
+    if _attn_hip(qkv, heads) and (drop is None or _attn_drop_hip(S, hd)):
         ext = _ext.load()
-        bg = hbias.grad if _trainable(hbias) and S <= ext.attn_max_seq() else None
+        bg = hbias.grad if _trainable(hbias) and ext.attn_fused_bias(S, hd) else None
         if drop is None:
             return ext.attn_bwd(do, qkv, o, lse, heads, bg), bg is not None
         return ext.attn_bwd(do, qkv, o, lse, heads, bg, drop[0], drop[1]), bg is not None
