@@ -1282,6 +1282,8 @@ int dispatch_sp(bool fwd, const uint16_t* qkv, const uint16_t* o, const uint16_t
 //                         delta = rowsum(dO * O) for the next kernel.
 //   attn_bwd_dkv_kernel   WG = 64 keys (key on the lane, K / V fragments kept in registers);
 //                         sweeps 64-query tiles: dV^T += dO^T P, dK^T += Q^T dS.
+// Each has a DROP instantiation (attention-probability dropout with the whole-sequence kernels'
+// mask: drop_keep_q4 / DropK below); the DROP = false ones carry no trace of it.
 // Every output element has one writer: no atomics, deterministic.  Grid x = (b, h) major, tile
 // minor, so the WGs sharing one (b, h)'s K / V (or Q / dO) rows are dispatched together.
 //
@@ -1366,10 +1368,61 @@ JM_DEVICE bf16x8_t tr_frag(const uint16_t* t, int s, int dt, int l16, int g) {
   return cat44(tr4(p), tr4(p + 16 * KS));
 }
 
-template <int HD>
+// Attention-probability dropout on the tile-streamed kernels (DROP): the mask, threshold and scale
+// of the whole-sequence kernels (AttnDrop above), hashed per 16-key tile right where the scores are
+// used, so nothing of the mask stays live across tiles.
+// Query on the lane (forward, dQ): keep bits of P[q][kb + 4 g + i], i = 0..3.  jl = the hash index
+// of the lane's own key pair at key base 0: (bh S + 4 g + 2 qodd) seh + (q >> 1); the lane hashes
+// keys 2 qodd, 2 qodd + 1 of its four and takes the other two from the lane of query q ^ 1 (same
+// lane group, same hash: the pair convention), as softmax_pv does.  Every lane must be active.
+struct DropQ {
+  uint64_t seed;
+  uint32_t seh, jl, thr;
+  int qodd;  // tile bases are multiples of 16, so the query's parity is the lane's
+};
+JM_DEVICE DropQ drop_q(const AttnDrop& d, int bh, int S, int q, int l16, int g) {
+  DropQ r;
+  r.seed = (uint64_t)d.seed[0];
+  r.seh = (uint32_t)((S + 1) >> 1);
+  r.qodd = l16 & 1;
+  r.jl = (uint32_t)(bh * S + 4 * g + 2 * r.qodd) * r.seh + (uint32_t)(q >> 1);
+  r.thr = d.thr;
+  return r;
+}
+JM_DEVICE void drop_keep_q4(bool (&kp)[4], const DropQ& d, int kb) {
+  uint32_t hm[2], hp[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) hm[u] = drop_hash(d.jl + (uint32_t)(kb + u) * d.seh, d.seed);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) hp[u] = dpp_mov_u32<0xB1>(hm[u]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) kp[i] = drop_keep_half((i >> 1) == d.qodd ? hm[i & 1] : hp[i & 1], d.qodd, d.thr);
+}
+
+// Key on the lane (dK / dV): four consecutive queries per accumulator -> one hash per query pair,
+// index jk + (query >> 1) with jk = (bh S + key) seh (the whole-sequence backward's form)
+struct DropK {
+  uint64_t seed;
+  uint32_t jk, thr;
+};
+JM_DEVICE DropK drop_k(const AttnDrop& d, int bh, int S, int key) {
+  return DropK{(uint64_t)d.seed[0], (uint32_t)(bh * S + key) * (uint32_t)((S + 1) >> 1), d.thr};
+}
+
+// kernel argument of the tile-streamed kernels: the DROP = false instantiations take an empty one,
+// so their code is what it was before dropout existed on this path
+struct NoDrop {};
+template <bool DROP>
+using DropArg = std::conditional_t<DROP, AttnDrop, NoDrop>;
+JM_DEVICE DropQ drop_q(const NoDrop&, int, int, int, int, int) { return DropQ{}; }
+JM_DEVICE DropK drop_k(const NoDrop&, int, int, int) { return DropK{}; }
+JM_DEVICE float drop_scale(const AttnDrop& d) { return d.scale; }
+JM_DEVICE float drop_scale(const NoDrop&) { return 1.f; }
+
+template <int HD, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* __restrict__ qkv,
                                                             uint16_t* __restrict__ o, float* __restrict__ lse,
-                                                            int S, int H, float scale) {
+                                                            int S, int H, float scale, DropArg<DROP> drop) {
   constexpr int KS = lks<HD>(), KK = lkp<HD>() / 32, DT = HD / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[LT * KS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[LT * KS];
@@ -1383,6 +1436,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* _
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l16 = lane & 15, g = lane >> 4;
   const int q = qb * LT + wave * 16 + l16;
   const float sl2 = scale * LOG2E;
+  const DropQ dq4 = drop_q(drop, bh, S, q, l16, g);
 
   bf16x8_t qf[KK];
 #pragma unroll
@@ -1444,6 +1498,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* _
     for (int s = 0; s < 2; ++s) {
       float pf[8] = {sc[2 * s][0], sc[2 * s][1], sc[2 * s][2], sc[2 * s][3],
                      sc[2 * s + 1][0], sc[2 * s + 1][1], sc[2 * s + 1][2], sc[2 * s + 1][3]};
+      if constexpr (DROP) {  // only P.V takes the masked P: m and l above are the undropped ones
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          bool kp[4];
+          drop_keep_q4(kp, dq4, k0 + 32 * s + 16 * t);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) pf[4 * t + i] = kp[i] ? pf[4 * t + i] : 0.f;
+        }
+      }
       const bf16x8_t pb = pack8(pf);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) oacc[dt] = mfma(tr_frag<HD>(Vs, s, dt, l16, g), pb, oacc[dt]);
@@ -1452,7 +1515,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* _
   l += __shfl_xor(l, 16, WAVE);
   l += __shfl_xor(l, 32, WAVE);
   if (q < S) {
-    const float inv = 1.f / l;
+    const float inv = drop_scale(drop) / l;
     uint16_t* orow = o + ((long)b * S + q) * H * HD + h * HD;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -1463,13 +1526,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_long_kernel(const uint16_t* _
   }
 }
 
-template <int HD>
+template <int HD, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ qkv,
                                                           const uint16_t* __restrict__ o,
                                                           const uint16_t* __restrict__ dO,
                                                           const float* __restrict__ lse,
                                                           uint16_t* __restrict__ dqkv, float* __restrict__ delta,
-                                                          int S, int H, float scale) {
+                                                          int S, int H, float scale, DropArg<DROP> drop) {
   constexpr int KS = lks<HD>(), KK = lkp<HD>() / 32, DT = HD / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[LT * KS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[LT * KS];
@@ -1483,6 +1546,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l16 = lane & 15, g = lane >> 4;
   const int q = qb * LT + wave * 16 + l16;
   const float sl2 = scale * LOG2E;
+  const DropQ dq4 = drop_q(drop, bh, S, q, l16, g);  // the forward's mask
 
   bf16x8_t qf[KK], df[KK];
   float dl = 0.f;
@@ -1531,10 +1595,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
         sa = mfma(ld8(Ks + (kt * 16 + l16) * KS + 32 * kk + 8 * g), qf[kk], sa);
         pa = mfma(ld8(Vs + (kt * 16 + l16) * KS + 32 * kk + 8 * g), df[kk], pa);
       }
+      bool kp[4];
+      if constexpr (DROP) drop_keep_q4(kp, dq4, k0 + kt * 16);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float p = k0 + kt * 16 + 4 * g + i < S ? __builtin_amdgcn_exp2f(sa[i] * sl2 - l2) : 0.f;
-        ds[kt][i] = p * (pa[i] - dl);
+        if constexpr (DROP)  // dS = P (M dP' / keep - delta); delta is that of the dropped O
+          ds[kt][i] = p * (kp[i] ? fmaf(pa[i], drop_scale(drop), -dl) : -dl);
+        else
+          ds[kt][i] = p * (pa[i] - dl);
       }
     }
 #pragma unroll
@@ -1556,12 +1625,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   }
 }
 
-template <int HD>
+template <int HD, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __restrict__ qkv,
                                                            const uint16_t* __restrict__ dO,
                                                            const float* __restrict__ lse,
                                                            const float* __restrict__ delta,
-                                                           uint16_t* __restrict__ dqkv, int S, int H, float scale) {
+                                                           uint16_t* __restrict__ dqkv, int S, int H, float scale,
+                                                           DropArg<DROP> drop) {
   constexpr int KS = lks<HD>(), KK = lkp<HD>() / 32, DT = HD / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Qs[LT * KS];
   __shared__ __attribute__((aligned(16))) uint16_t Ds[LT * KS];
@@ -1578,6 +1648,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
   const int key = kb * LT + wave * 16 + l16;
   const bool kv = key < S;
   const float sl2 = scale * LOG2E;
+  const DropK dk2 = drop_k(drop, bh, S, key);
 
   bf16x8_t kf[KK], vf[KK];
 #pragma unroll
@@ -1632,12 +1703,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
           pa = mfma(ld8(Ds + (qt * 16 + l16) * KS + 32 * kk + 8 * g), vf[kk], pa);
         }
         // sa[i] = S[query = qt*16 + 4g + i][key = l16]
+        uint32_t dh[2] = {0u, 0u};  // one hash per query pair (q0 + qt*16 + 4g even)
+        if constexpr (DROP) {
+#pragma unroll
+          for (int u = 0; u < 2; ++u) dh[u] = drop_hash(dk2.jk + (uint32_t)(((q0 + qt * 16 + 4 * g) >> 1) + u), dk2.seed);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int qq = qt * 16 + 4 * g + i;
           const float p = kv ? __builtin_amdgcn_exp2f(sa[i] * sl2 - Ls[qq]) : 0.f;
-          pf[4 * t + i] = p;
-          df[4 * t + i] = p * (pa[i] - Dl[qq]);
+          if constexpr (DROP) {  // dV^T += dO^T (M P) (1 / keep at the store), dS = P (M dP' / keep - delta)
+            const bool kp = drop_keep_half(dh[i >> 1], i & 1, dk2.thr);
+            pf[4 * t + i] = kp ? p : 0.f;
+            df[4 * t + i] = p * (kp ? fmaf(pa[i], drop_scale(drop), -Dl[qq]) : -Dl[qq]);
+          } else {
+            pf[4 * t + i] = p;
+            df[4 * t + i] = p * (pa[i] - Dl[qq]);
+          }
         }
       }
       const bf16x8_t pb = pack8(pf), db = pack8(df);
@@ -1654,7 +1736,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       float a[4] = {dk[dt][0] * scale, dk[dt][1] * scale, dk[dt][2] * scale, dk[dt][3] * scale};
-      float c[4] = {dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]};
+      const float vs = drop_scale(drop);
+      float c[4] = {dv[dt][0] * vs, dv[dt][1] * vs, dv[dt][2] * vs, dv[dt][3] * vs};
       store4(row + (H + h) * HD + dt * 16 + 4 * g, a);
       store4(row + (2 * H + h) * HD + dt * 16 + 4 * g, c);
     }
@@ -1662,20 +1745,29 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
 }
 
 template <int HD>
-int run_long_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int H, float scale, hipStream_t st) {
+int run_long_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int H, float scale, AttnDrop dr,
+                 hipStream_t st) {
   const long grid = (long)B * H * ((S + LT - 1) / LT);
   if (grid > 0x7fffffffL) return -5;
-  attn_fwd_long_kernel<HD><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, o, lse, S, H, scale);
+  if (dr.seed != nullptr)
+    attn_fwd_long_kernel<HD, true><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, o, lse, S, H, scale, dr);
+  else
+    attn_fwd_long_kernel<HD, false><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, o, lse, S, H, scale, NoDrop{});
   return 0;
 }
 
 template <int HD>
 int run_long_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv,
-                 float* delta, int B, int S, int H, float scale, hipStream_t st) {
+                 float* delta, int B, int S, int H, float scale, AttnDrop dr, hipStream_t st) {
   const long grid = (long)B * H * ((S + LT - 1) / LT);
   if (grid > 0x7fffffffL) return -5;
-  attn_bwd_dq_kernel<HD><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, o, dO, lse, dqkv, delta, S, H, scale);
-  attn_bwd_dkv_kernel<HD><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, dO, lse, delta, dqkv, S, H, scale);
+  if (dr.seed != nullptr) {
+    attn_bwd_dq_kernel<HD, true><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, o, dO, lse, dqkv, delta, S, H, scale, dr);
+    attn_bwd_dkv_kernel<HD, true><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, dO, lse, delta, dqkv, S, H, scale, dr);
+  } else {
+    attn_bwd_dq_kernel<HD, false><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, o, dO, lse, dqkv, delta, S, H, scale, NoDrop{});
+    attn_bwd_dkv_kernel<HD, false><<<dim3((unsigned)grid), 256, 0, st>>>(qkv, dO, lse, delta, dqkv, S, H, scale, NoDrop{});
+  }
   return 0;
 }
 
@@ -1696,8 +1788,7 @@ static bool whole_seq_hd(int hd) { return hd == 32 || hd == 64; }
 static bool tiled_only_hd(int hd) { return hd == 80 || hd == 96 || hd == 128; }
 
 // 1: (S, hd) runs on the tile-streamed kernels -- jm_attn_fwd takes them itself, the backward is
-// jm_attn_bwd_long (delta workspace, no dropout); 0: on the whole-sequence kernels (jm_attn_bwd)
-// or unsupported
+// jm_attn_bwd_long (delta workspace); 0: on the whole-sequence kernels (jm_attn_bwd) or unsupported
 int jm_attn_tiled(int S, int hd) { return tiled_only_hd(hd) || (whole_seq_hd(hd) && S > ATTN_MAX_SEQ); }
 
 // 1 exactly where the backward can add the QKV bias gradient (jm_attn_bwd's dbias_part): the
@@ -1711,19 +1802,22 @@ int jm_attn_bwd_part_rows(int B, int S, int hd) {
   return (B + BWD2_PPW - 1) / BWD2_PPW;
 }
 
+// 1 wherever a kernel takes a dropout seed: every (S, hd) with kernels, on both families
+int jm_attn_dropout(int S, int hd) { return S >= 1 && (whole_seq_hd(hd) || tiled_only_hd(hd)); }
+
 // dseed (int64 [1] on the device) non-null: dropout on the attention probabilities with keep
-// threshold dthr = round(keep * 65536) and dscale = 1 / keep (whole-sequence kernels, S <= 224)
+// threshold dthr = round(keep * 65536) and dscale = 1 / keep, on both kernel families (one mask
+// convention: AttnDrop)
 int jm_attn_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int H, int hd, const int64_t* dseed,
                 uint32_t dthr, float dscale, hipStream_t st) {
   const float scale = 1.f / sqrtf((float)hd);
   const AttnDrop dr{dseed, dthr, dscale};
   if (jm_attn_tiled(S, hd)) {
-    if (dseed != nullptr) return -5;
-    if (hd == 32) return run_long_fwd<32>(qkv, o, lse, B, S, H, scale, st);
-    if (hd == 64) return run_long_fwd<64>(qkv, o, lse, B, S, H, scale, st);
-    if (hd == 80) return run_long_fwd<80>(qkv, o, lse, B, S, H, scale, st);
-    if (hd == 96) return run_long_fwd<96>(qkv, o, lse, B, S, H, scale, st);
-    if (hd == 128) return run_long_fwd<128>(qkv, o, lse, B, S, H, scale, st);
+    if (hd == 32) return run_long_fwd<32>(qkv, o, lse, B, S, H, scale, dr, st);
+    if (hd == 64) return run_long_fwd<64>(qkv, o, lse, B, S, H, scale, dr, st);
+    if (hd == 80) return run_long_fwd<80>(qkv, o, lse, B, S, H, scale, dr, st);
+    if (hd == 96) return run_long_fwd<96>(qkv, o, lse, B, S, H, scale, dr, st);
+    if (hd == 128) return run_long_fwd<128>(qkv, o, lse, B, S, H, scale, dr, st);
     return -1;
   }
   if (hd == 32) return dispatch_sp<32>(true, qkv, nullptr, nullptr, nullptr, o, lse, B, S, H, scale, dr, st);
@@ -1746,15 +1840,17 @@ int jm_attn_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, cons
 }
 
 // jm_attn_tiled(S, hd): tile-streamed backward; delta = fp32 [B][H][S] workspace.  No fused
-// bias colsum on this path (the caller takes colsum(dqkv)).
+// bias colsum on this path (the caller takes colsum(dqkv)).  dseed / dthr / dscale: the forward's.
 int jm_attn_bwd_long(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv,
-                     float* delta, int B, int S, int H, int hd, hipStream_t st) {
+                     float* delta, int B, int S, int H, int hd, const int64_t* dseed, uint32_t dthr, float dscale,
+                     hipStream_t st) {
   const float scale = 1.f / sqrtf((float)hd);
-  if (hd == 32) return run_long_bwd<32>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
-  if (hd == 64) return run_long_bwd<64>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
-  if (hd == 80) return run_long_bwd<80>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
-  if (hd == 96) return run_long_bwd<96>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
-  if (hd == 128) return run_long_bwd<128>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, st);
+  const AttnDrop dr{dseed, dthr, dscale};
+  if (hd == 32) return run_long_bwd<32>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, dr, st);
+  if (hd == 64) return run_long_bwd<64>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, dr, st);
+  if (hd == 80) return run_long_bwd<80>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, dr, st);
+  if (hd == 96) return run_long_bwd<96>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, dr, st);
+  if (hd == 128) return run_long_bwd<128>(qkv, o, dO, lse, dqkv, delta, B, S, H, scale, dr, st);
   return -1;
 }
 

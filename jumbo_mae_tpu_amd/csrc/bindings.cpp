@@ -70,7 +70,9 @@ int jm_attn_tiled(int S, int hd);
 int jm_attn_fused_bias(int S, int hd);
 int jm_attn_bwd_part_rows(int B, int S, int hd);
 int jm_attn_bwd_long(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv,
-                     float* delta, int B, int S, int H, int hd, hipStream_t st);
+                     float* delta, int B, int S, int H, int hd, const int64_t* dseed, uint32_t dthr, float dscale,
+                     hipStream_t st);
+int jm_attn_dropout(int S, int hd);
 void jm_opt_sumsq(const float* x, const int* chunks, int nchunks, float* out, float* cpart, hipStream_t st);
 void jm_zero_f32(float* p, long n, hipStream_t st);
 void jm_opt_adamw(float* p, const float* g, float* mu, float* nu, uint16_t* shadow, const int* chunks, int nchunks,
@@ -417,11 +419,9 @@ torch::Tensor residual_bwd(torch::Tensor dout, c10::optional<torch::Tensor> y, c
 // seed (int64 [1] on the device) with rate > 0: dropout on the attention probabilities (mask:
 // common.h drop_keep at ((b H + h) S + q) SE + k, the backward regenerates it from the same seed)
 static std::tuple<const int64_t*, uint32_t, float> attn_drop(const c10::optional<torch::Tensor>& seed, double rate,
-                                                             const torch::Tensor& like, int S, int hd) {
+                                                             const torch::Tensor& like) {
   if (!seed.has_value() || !seed->defined() || rate <= 0.0) return {nullptr, 0u, 1.f};
   check_seed(*seed, like);
-  TORCH_CHECK(S <= jm_attn_max_seq(), "attention dropout: S <= ", jm_attn_max_seq(), " (whole-sequence kernels)");
-  TORCH_CHECK(!jm_attn_tiled(S, hd), "attention dropout: head dim ", hd, " runs on the tile-streamed kernels (no dropout)");
   const auto kp = keep_params(rate);
   return {seed->data_ptr<int64_t>(), kp.first, kp.second};
 }
@@ -439,6 +439,9 @@ py::tuple attn_head_dims() {
 // the tile-streamed ones (S > attn_max_seq(), head dims 80 / 96 / 128 at any S) leave it to the caller
 bool attn_fused_bias(int64_t S, int64_t hd) { return jm_attn_fused_bias((int)S, (int)hd) != 0; }
 
+// whether attn_fwd / attn_bwd take a dropout seed at (S, hd): wherever there is a kernel
+bool attn_dropout(int64_t S, int64_t hd) { return jm_attn_dropout((int)S, (int)hd) != 0; }
+
 static void check_attn_shape(const torch::Tensor& qkv, int64_t heads, const char* what) {
   TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) % (3 * heads) == 0, what,
               ": qkv must be [B, S, 3 * heads * hd]");
@@ -452,7 +455,7 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t heads, c10::optio
   const int D = D3 / 3, hd = D / heads;
   auto o = torch::empty({B, S, D}, qkv.options());
   auto lse = torch::empty({B, (long)heads, S}, qkv.options().dtype(torch::kFloat32));
-  const auto dr = attn_drop(seed, rate, qkv, S, hd);
+  const auto dr = attn_drop(seed, rate, qkv);
   check_rc(jm_attn_fwd(bf(qkv), bfm(o), lse.data_ptr<float>(), B, S, heads, hd, std::get<0>(dr), std::get<1>(dr),
                        std::get<2>(dr), stream()),
            "attn_fwd");
@@ -473,13 +476,13 @@ torch::Tensor attn_bwd(torch::Tensor dO, torch::Tensor qkv, torch::Tensor o, tor
   TORCH_CHECK(dO.numel() == (long)B * S * D && o.numel() == (long)B * S * D && lse.numel() == (long)B * heads * S,
               "attn_bwd: dO / o must hold [B, S, D] and lse [B, H, S]");
   auto dqkv = torch::empty_like(qkv);
-  const auto dr = attn_drop(seed, rate, qkv, S, hd);
+  const auto dr = attn_drop(seed, rate, qkv);
   if (jm_attn_tiled(S, hd)) {  // tile-streamed kernels; the caller reduces the bias gradient
     TORCH_CHECK(!dbias, "attn_bwd: no fused bias gradient at S = ", S, ", head dim ", hd,
                 " (tile-streamed kernels; see attn_fused_bias)");
     auto delta = torch::empty({B, (long)heads, S}, qkv.options().dtype(torch::kFloat32));
     check_rc(jm_attn_bwd_long(bf(qkv), bf(o), bf(dO), lse.data_ptr<float>(), bfm(dqkv), delta.data_ptr<float>(), B,
-                              S, heads, hd, stream()),
+                              S, heads, hd, std::get<0>(dr), std::get<1>(dr), std::get<2>(dr), stream()),
              "attn_bwd (long)");
     return dqkv;
   }
@@ -1293,6 +1296,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_max_seq", &jm_attn_max_seq);
   m.def("attn_head_dims", &attn_head_dims);
   m.def("attn_fused_bias", &attn_fused_bias, py::arg("S"), py::arg("hd"));
+  m.def("attn_dropout", &attn_dropout, py::arg("S"), py::arg("hd"));
   m.def("gemm_tn_wgrad", &gemm_tn_wgrad, py::arg("dy"), py::arg("x"), py::arg("g"), py::arg("store") = false);
   m.def("gemm_tn_wgrad_seg", &gemm_tn_wgrad_seg, py::arg("dys"), py::arg("xs"), py::arg("g"), py::arg("store") = false);
   m.def("zero_ranges", &zero_ranges, "zero float ranges of a flat buffer (one launch)");

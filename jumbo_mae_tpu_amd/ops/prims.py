@@ -747,10 +747,17 @@ def _attn_hip(qkv: torch.Tensor, heads: int) -> bool:
     return hd in _ext.load().attn_head_dims()
 
 
+# False: attention-probability dropout on the tile-streamed kernels (S > attn_max_seq(), head dims
+# 80 / 96 / 128) takes the composition below instead -- an A/B switch for tests (identical seeds,
+# identical mask), not a fallback
+_ATTN_DROP_TILED = True
+
+
 def _attn_drop_hip(S: int, hd: int) -> bool:
-    """Attention-probability dropout is fused into the whole-sequence kernels only -- the (S, hd)
-    where the backward also fuses the bias gradient; elsewhere dropout takes the composition."""
-    return _ext.load().attn_fused_bias(S, hd)
+    """Attention-probability dropout is fused into both kernel families: wherever the extension
+    takes a seed (``attn_dropout``), which is every (S, hd) with HIP attention kernels."""
+    ext = _ext.load()
+    return ext.attn_dropout(S, hd) and (_ATTN_DROP_TILED or ext.attn_fused_bias(S, hd))
 
 
 def _drop_mask(drop, B: int, heads: int, S: int, device):
@@ -765,9 +772,8 @@ def _drop_mask(drop, B: int, heads: int, S: int, device):
 
 def attn_fwd(qkv: torch.Tensor, heads: int, drop=None):
     """qkv [B, S, 3*D] -> (o [B, S, D], lse [B, H, S]).  ``drop`` = (seed int64 [1] tensor, rate):
-    dropout on the attention probabilities (reference modeling.py:137), fused into the
-    whole-sequence kernels (head dims 32 / 64 up to S = attn_max_seq()); lse is that of the
-    undropped softmax."""
+    dropout on the attention probabilities (reference modeling.py:137), fused into the HIP kernels
+    at every supported head dim and length; lse is that of the undropped softmax."""
     B, S, three_d = qkv.shape
     D = three_d // 3
     hd = D // heads

@@ -3,12 +3,15 @@ tile-streamed kernels at the ViT-H/14 shapes (head dim 80) beside the PyTorch co
 
     python tools/attn_bench.py [--iters N] [--shapes dec,enc]
     python tools/attn_bench.py --shapes vith_enc --torch     # adds the composition column
+    python tools/attn_bench.py --shapes vith_ft --dropout 0.1   # attention-probability dropout
 
 Prints one line per (shape, pass) with us/call and achieved TFLOP/s (useful flops only).  With
 ``--torch`` each line also carries the time of ``ops/prims.py`` attn_fwd / attn_bwd with the HIP
 route disabled in-process -- the composition with fp32 [B, H, S, S] score tensors, the path of
 head dims without kernels -- and a last line per shape gives forward + backward and the peak
-memory (torch.cuda.max_memory_allocated) of one forward + backward each way.  Times are medians of
+memory (torch.cuda.max_memory_allocated) of one forward + backward each way.  With ``--dropout RATE``
+the same calls carry a seed (the mask is regenerated in the kernels; the composition builds it on
+the CPU, ops/prims.py _drop_mask) and no fused bias gradient is requested.  Times are medians of
 ``--reps`` windows of ``--iters`` calls after a warm-up; run one shape per process to compare
 shapes."""
 
@@ -27,7 +30,9 @@ from jumbo_mae_tpu_amd.ops import prims as P  # noqa: E402
 
 SHAPES = {"dec": (512, 199, 16, 32), "dec2k": (2048, 199, 16, 32), "enc": (512, 52, 16, 64), "enc2k": (2048, 52, 16, 64), "ft": (128, 199, 16, 64), "ft12": (128, 199, 12, 64),
           # ViT-H/14 at 224 px: encoder pretrain (64 kept + 3 CLS), finetune (256 + 3), and one hd-128 shape
-          "vith_enc": (64, 67, 16, 80), "vith_ft": (32, 259, 16, 80), "hd128": (32, 199, 8, 128)}
+          "vith_enc": (64, 67, 16, 80), "vith_ft": (32, 259, 16, 80), "hd128": (32, 199, 8, 128),
+          # finetune at 448 px (ViT-B/16): 784 + 3 tokens
+          "ft448": (8, 787, 12, 64)}
 
 
 def _time(fn, iters, reps):
@@ -73,6 +78,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="dec,enc")
     ap.add_argument("--torch", action="store_true", help="also time the PyTorch composition (ops/prims.py, HIP route off)")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="RATE",
+                    help="attention-probability dropout at this rate (0: none)")
     a = ap.parse_args()
     ext = _ext.load()
     for name in a.shapes.split(","):
@@ -80,13 +87,18 @@ def main():
         D = H * hd
         qkv = (torch.randn(B, S, 3 * D, device="cuda") * 1.5).bfloat16()
         do = torch.randn(B, S, D, device="cuda").bfloat16()
-        db = torch.zeros(3 * D, device="cuda") if ext.attn_fused_bias(S, hd) else None
-        o, lse = ext.attn_fwd(qkv, H)
+        db = torch.zeros(3 * D, device="cuda") if ext.attn_fused_bias(S, hd) and not a.dropout else None
+        seed = torch.tensor([0x5EED_1234_5678], dtype=torch.int64, device="cuda") if a.dropout else None
+        drop = (seed, a.dropout) if a.dropout else None
+        o, lse = ext.attn_fwd(qkv, H, seed, a.dropout)
         fl_f = 4.0 * B * H * S * S * hd
         tot = [0.0, 0.0]
-        for label, fn, tfn, fl in (("fwd", lambda: ext.attn_fwd(qkv, H), lambda: P.attn_fwd(qkv, H), fl_f),
-                                   ("bwd", lambda: ext.attn_bwd(do, qkv, o, lse, H, db),
-                                    lambda: P.attn_bwd(do, qkv, o, lse, H), 2.5 * fl_f)):
+        if a.dropout:
+            name = f"{name}+drop{a.dropout:g}"
+        for label, fn, tfn, fl in (("fwd", lambda: ext.attn_fwd(qkv, H, seed, a.dropout),
+                                    lambda: P.attn_fwd(qkv, H, drop=drop), fl_f),
+                                   ("bwd", lambda: ext.attn_bwd(do, qkv, o, lse, H, db, seed, a.dropout),
+                                    lambda: P.attn_bwd(do, qkv, o, lse, H, drop=drop), 2.5 * fl_f)):
             us = _time(fn, a.iters, a.reps)
             tot[0] += us
             line = f"{name} {label} B={B} S={S} H={H} hd={hd}: {us:8.1f} us  {fl / us / 1e6:7.1f} TF/s"
@@ -98,8 +110,8 @@ def main():
             print(line, flush=True)
         if a.torch:
             def both():
-                o2, l2 = P.attn_fwd(qkv, H)
-                P.attn_bwd(do, qkv, o2, l2, H)
+                o2, l2 = P.attn_fwd(qkv, H, drop=drop)
+                P.attn_bwd(do, qkv, o2, l2, H, drop=drop)
 
             m_hip = _peak_mib(both)
             with _composition():
