@@ -25,6 +25,11 @@ int jm_debug_line_augment();
 int jm_rrc_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t* tmp, int tmp_rows_max, uint8_t* out,
                   hipStream_t st);
 int jm_rrc_kmax();
+int jm_debug_line_augment_chain();
+int jm_aug_stat_words();
+int jm_aug_record_len();
+int jm_aug_chain(uint8_t* images, uint8_t* scratch, const double* chain, int B, int slots, int S, uint32_t* stats,
+                 hipStream_t st);
 int jm_dropout_apply(const void* x, void* y, long n, int bf16, const int64_t* seed, uint32_t thr, float scale,
                      hipStream_t st);
 int jm_gelu_drop(const uint16_t* h, uint16_t* g, uint16_t* gp, long n, const int64_t* seed, uint32_t thr, float scale,
@@ -904,6 +909,34 @@ torch::Tensor rrc_resize(torch::Tensor src, torch::Tensor tab, int64_t size, int
   return out;
 }
 
+// RandAugment / AutoAugment / ColorJitter op chains on the resized batch (csrc/augment_chain.hip):
+// images uint8 [B, 3, S, S] (rrc_resize's result; CONSUMED -- it is one of the two ping-pong
+// buffers), chain float64 [B, slots, P] records (data/autoaugment.py), scratch the other buffer.
+// Returns whichever of the two holds the result.  Stream-ordered, no host sync.
+torch::Tensor aug_chain(torch::Tensor images, torch::Tensor chain, torch::Tensor scratch) {
+  CHECK_CUDA(images);
+  CHECK_CUDA(chain);
+  CHECK_CUDA(scratch);
+  CHECK_DT(images, torch::kUInt8);
+  CHECK_DT(scratch, torch::kUInt8);
+  CHECK_DT(chain, torch::kFloat64);
+  TORCH_CHECK(images.dim() == 4 && images.size(1) == 3 && images.size(2) == images.size(3) && images.is_contiguous(),
+              "aug_chain: images must be contiguous uint8 [B, 3, S, S]");
+  TORCH_CHECK(scratch.sizes() == images.sizes() && scratch.is_contiguous() && scratch.data_ptr() != images.data_ptr(),
+              "aug_chain: scratch must be a second contiguous buffer of the images' shape");
+  TORCH_CHECK(chain.dim() == 3 && chain.size(0) == images.size(0) && chain.size(2) == jm_aug_record_len() &&
+                  chain.is_contiguous(),
+              "aug_chain: chain must be contiguous float64 [B, slots, ", jm_aug_record_len(), "]");
+  TORCH_CHECK(images.size(0) > 0 && images.size(2) <= 4096, "aug_chain: bad sizes");
+  const int B = images.size(0);
+  auto stats = torch::empty({B, jm_aug_stat_words()}, images.options().dtype(torch::kInt32));
+  const int rc = jm_aug_chain(images.data_ptr<uint8_t>(), scratch.data_ptr<uint8_t>(), chain.data_ptr<double>(), B,
+                              (int)chain.size(1), (int)images.size(2),
+                              reinterpret_cast<uint32_t*>(stats.data_ptr<int32_t>()), stream());
+  check_rc(rc < 0 ? rc : 0, "aug_chain");
+  return rc == 1 ? scratch : images;
+}
+
 // ---------------------------------------------------------------- dropout (csrc/dropout.hip)
 
 // y = x * keep(seed, i) / keep  (bf16 or fp32, contiguous, numel % 8 == 0); also its own backward
@@ -1244,7 +1277,7 @@ py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
       {"attention", jm_debug_line_attention}, {"dropout", jm_debug_line_dropout},
-      {"augment", jm_debug_line_augment},
+      {"augment", jm_debug_line_augment},     {"augment_chain", jm_debug_line_augment_chain},
       {"elementwise", jm_debug_line_elementwise},
       {"gemm", jm_debug_line_gemm},           {"gemm_tn", jm_debug_line_gemm_tn},
       {"layernorm", jm_debug_line_layernorm}, {"mae", jm_debug_line_mae},
@@ -1274,6 +1307,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rrc_resize", &rrc_resize, py::arg("src"), py::arg("tab"), py::arg("size"), py::arg("tmp_bytes"),
         py::arg("tmp_rows_max"));
   m.def("rrc_kmax", &jm_rrc_kmax);
+  m.def("aug_chain", &aug_chain, py::arg("images"), py::arg("chain"), py::arg("scratch"));
   m.def("gelu_drop", &gelu_drop, py::arg("a"), py::arg("b") = py::none(), py::arg("seed"), py::arg("rate"));
   m.def("softmax_dropout_fwd", &softmax_dropout_fwd);
   m.def("softmax_dropout_bwd", &softmax_dropout_bwd);

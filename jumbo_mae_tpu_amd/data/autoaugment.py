@@ -10,6 +10,7 @@ per-op probability p=0.5), ``augmix-m3-w3-d-1`` (width, depth, alpha, blended), 
 
 from __future__ import annotations
 
+import math
 import random
 
 import numpy as np
@@ -162,6 +163,87 @@ NAME_TO_OP = {
     "TranslateY": translate_y_abs, "TranslateXRel": translate_x_rel, "TranslateYRel": translate_y_rel,
 }
 
+# ---- describing twins (device augment): the same ``random`` draws in the same order as the ops
+# above, no pixels touched; the result is one op record for csrc/augment_chain.hip (mirrored by
+# data/augment_ref.py).  Record = float64 x AUG_P: kind, scalar argument (bits / threshold / add /
+# blend factor), the 6 coefficients of Image.transform(AFFINE), resample (2 bilinear, 3 bicubic),
+# fill colour r, g, b.
+AUG_P = 12
+(K_IDENTITY, K_INVERT, K_POSTERIZE, K_SOLARIZE, K_SOLARIZE_ADD, K_AUTOCONTRAST, K_EQUALIZE, K_COLOR, K_BRIGHTNESS,
+ K_CONTRAST, K_SHARPNESS, K_AFFINE) = range(12)
+AUG_KINDS = 12
+
+
+def op_record(kind=K_IDENTITY, arg=0.0, matrix=(1, 0, 0, 0, 1, 0), resample=0, fill=(0, 0, 0)) -> np.ndarray:
+    return np.array([kind, arg, *matrix, int(resample), *fill], dtype=np.float64)
+
+
+def rotate_matrix(deg: float, w: int, h: int):
+    """The matrix ``Image.rotate(deg)`` (no expand / center / translate) hands to ``transform``,
+    with its rounding; None where PIL returns a copy (deg a multiple of 360)."""
+    angle = deg % 360.0
+    if angle == 0:
+        return None
+    cx, cy = w / 2.0, h / 2.0
+    angle = -math.radians(angle)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0,
+         round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def _d_affine(matrix, hp):
+    # as _affine: the matrix argument (its _neg draw) is evaluated before the resample choice
+    return op_record(K_AFFINE, 0.0, matrix, random.choice(_RESAMPLE), hp.get("img_mean", _FILL))
+
+
+def _d_rotate(lvl, hp, size):
+    deg = _neg(lvl / _MAX * 30.0)
+    resample = random.choice(_RESAMPLE)
+    m = rotate_matrix(deg, size, size)
+    return op_record() if m is None else op_record(K_AFFINE, 0.0, m, resample, hp.get("img_mean", _FILL))
+
+
+def _d_posterize(bits):
+    bits = int(bits)
+    return op_record() if bits >= 8 else op_record(K_POSTERIZE, max(bits, 0))
+
+
+def _d_translate_rel(lvl, hp, size, axis):
+    px = _neg(lvl / _MAX * hp.get("translate_pct", 0.45)) * size
+    return _d_affine((1, 0, px, 0, 1, 0) if axis == 0 else (1, 0, 0, 0, 1, px), hp)
+
+
+# name -> (level, hparams, image size) -> record
+NAME_TO_DESCRIBE = {
+    "AutoContrast": lambda lvl, hp, s: op_record(K_AUTOCONTRAST),
+    "Equalize": lambda lvl, hp, s: op_record(K_EQUALIZE),
+    "Invert": lambda lvl, hp, s: op_record(K_INVERT),
+    "Rotate": _d_rotate,
+    "Posterize": lambda lvl, hp, s: _d_posterize(int(lvl / _MAX * 4)),
+    "PosterizeIncreasing": lambda lvl, hp, s: _d_posterize(4 - int(lvl / _MAX * 4)),
+    "PosterizeOriginal": lambda lvl, hp, s: _d_posterize(int(lvl / _MAX * 4) + 4),
+    "Solarize": lambda lvl, hp, s: op_record(K_SOLARIZE, int(lvl / _MAX * 256)),
+    "SolarizeIncreasing": lambda lvl, hp, s: op_record(K_SOLARIZE, 256 - int(lvl / _MAX * 256)),
+    "SolarizeAdd": lambda lvl, hp, s: op_record(K_SOLARIZE_ADD, int(lvl / _MAX * 110)),
+    "Color": lambda lvl, hp, s: op_record(K_COLOR, _enh_level(lvl)),
+    "ColorIncreasing": lambda lvl, hp, s: op_record(K_COLOR, _enh_inc_level(lvl)),
+    "Contrast": lambda lvl, hp, s: op_record(K_CONTRAST, _enh_level(lvl)),
+    "ContrastIncreasing": lambda lvl, hp, s: op_record(K_CONTRAST, _enh_inc_level(lvl)),
+    "Brightness": lambda lvl, hp, s: op_record(K_BRIGHTNESS, _enh_level(lvl)),
+    "BrightnessIncreasing": lambda lvl, hp, s: op_record(K_BRIGHTNESS, _enh_inc_level(lvl)),
+    "Sharpness": lambda lvl, hp, s: op_record(K_SHARPNESS, _enh_level(lvl)),
+    "SharpnessIncreasing": lambda lvl, hp, s: op_record(K_SHARPNESS, _enh_inc_level(lvl)),
+    "ShearX": lambda lvl, hp, s: _d_affine((1, _neg(lvl / _MAX * 0.3), 0, 0, 1, 0), hp),
+    "ShearY": lambda lvl, hp, s: _d_affine((1, 0, 0, _neg(lvl / _MAX * 0.3), 1, 0), hp),
+    "TranslateX": lambda lvl, hp, s: _d_affine((1, 0, _neg(lvl / _MAX * hp.get("translate_const", 250)), 0, 1, 0), hp),
+    "TranslateY": lambda lvl, hp, s: _d_affine((1, 0, 0, 0, 1, _neg(lvl / _MAX * hp.get("translate_const", 250))), hp),
+    "TranslateXRel": lambda lvl, hp, s: _d_translate_rel(lvl, hp, s, 0),
+    "TranslateYRel": lambda lvl, hp, s: _d_translate_rel(lvl, hp, s, 1),
+}
+
 RAND_TRANSFORMS = ["AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color",
                    "Contrast", "Brightness", "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel"]
 RAND_INCREASING_TRANSFORMS = ["AutoContrast", "Equalize", "Invert", "Rotate", "PosterizeIncreasing",
@@ -190,6 +272,16 @@ class AugmentOp:
         m = max(0.0, min(m, self.mmax))
         return self.fn(img, m, self.hp)
 
+    def describe(self, size: int) -> np.ndarray:
+        """The record of this op on a ``size`` x ``size`` image: __call__'s draws, no pixels."""
+        if self.prob < 1.0 and random.random() > self.prob:
+            return op_record()
+        m = self.magnitude
+        if self.mstd > 0:
+            m = random.uniform(0, m) if self.mstd == float("inf") else random.gauss(m, self.mstd)
+        m = max(0.0, min(m, self.mmax))
+        return NAME_TO_DESCRIBE[self.name](m, self.hp, size)
+
 
 def _parse(spec: str):
     parts = spec.split("-")
@@ -204,6 +296,11 @@ class RandAugment:
         for op in random.choices(self.ops, k=self.n):
             img = op(img)
         return img
+
+    slots = property(lambda self: self.n)
+
+    def describe(self, size: int) -> list:
+        return [op.describe(size) for op in random.choices(self.ops, k=self.n)]
 
 
 def rand_augment_transform(spec: str, hparams: dict) -> RandAugment:
@@ -352,6 +449,11 @@ class AutoAugment:
         for op in random.choice(self.policy):
             img = op(img)
         return img
+
+    slots = property(lambda self: max(len(sp) for sp in self.policy))
+
+    def describe(self, size: int) -> list:
+        return [op.describe(size) for op in random.choice(self.policy)]
 
 
 def auto_augment_transform(spec: str, hparams: dict) -> AutoAugment:

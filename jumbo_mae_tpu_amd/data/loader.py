@@ -15,6 +15,11 @@ Reference ``create_dataloaders`` (/root/reference/src/dataset.py:100-161) with h
   a descriptor (``DeviceRRCParams``, packed per batch by ``collate_packed``); the resize and flip
   run on the GPU (csrc/augment.hip), bit-exact to PIL's bicubic, when ``DevicePrefetcher`` lands
   the batch.  A worker then spends its time on the JPEG decode only (profiles/r5_data_rate.txt).
+  ``--device-augment on`` also covers the finetune transform -- RandAugment / AutoAugment and
+  ColorJitter after the crop (``DeviceTrainParams``): the worker makes their draws too and ships a
+  chain of op records per image, which csrc/augment_chain.hip applies after the resize, bit-exact
+  to PIL (data/augment_ref.py is the NumPy mirror).  AugMix, random erasing and the ``src`` /
+  ``none`` crops stay on the host.
 Per-rank split replaces the reference's per-host split (one process per GPU here).
 """
 
@@ -40,12 +45,14 @@ RRC_KMAX = 24  # csrc/augment.hip taps per output pixel
 
 class PackedImages(NamedTuple):
     """A batch for the device augment: concatenated HWC uint8 crop windows + [B, 13] descriptors
-    (csrc/augment.hip), the scratch size of the horizontal pass and the output size."""
+    (csrc/augment.hip), the scratch size of the horizontal pass and the output size; ``chain``:
+    float64 [B, slots, AUG_P] op records applied after the resize (csrc/augment_chain.hip), or None."""
     src: torch.Tensor
     tab: torch.Tensor
     tmp_bytes: int
     rows_max: int
     size: int
+    chain: torch.Tensor | None = None
 
 
 def _span(n: int, a: int, c: int, out: int) -> tuple[int, int]:
@@ -89,36 +96,89 @@ class DeviceRRCParams:
         return win, np.array([0, y1 - y0, x1 - x0, y0, x0, H, W, i, j, ch, cw, flip, 0], dtype=np.int64)
 
 
+class DeviceTrainParams(DeviceRRCParams):
+    """Worker side of the device augment for the finetune transform: ``DeviceRRCParams``, then the
+    draws of RandAugment / AutoAugment (``aa``) and ColorJitter (``cj``) in the PIL path's order.
+    Returns (window, descriptor, chain): chain = float64 [slots, AUG_P] op records
+    (data/autoaugment.py), identity-padded to the transform's fixed slot count."""
+
+    def __init__(self, size: int, aa=None, cj=None):
+        super().__init__(size)
+        self.stages = [t for t in (aa, cj) if t is not None]
+        self.slots = sum(t.slots for t in self.stages)
+
+    def __call__(self, img):
+        from .autoaugment import op_record
+        win, desc = super().__call__(img)
+        recs = [r for t in self.stages for r in t.describe(self.size)]
+        recs += [op_record()] * (self.slots - len(recs))
+        return win, desc, np.stack(recs)
+
+
+def check_chain(chain: np.ndarray) -> np.ndarray:
+    """Host-side validation of a [B, slots, AUG_P] record table: known kinds and resample modes only."""
+    from .autoaugment import AUG_KINDS, AUG_P, K_AFFINE
+    if chain.ndim != 3 or chain.shape[2] != AUG_P or chain.dtype != np.float64:
+        raise ValueError(f"op chain must be float64 [B, slots, {AUG_P}], got {chain.dtype} {chain.shape}")
+    kinds = chain[:, :, 0]
+    if not np.all((kinds == np.floor(kinds)) & (kinds >= 0) & (kinds < AUG_KINDS)):
+        raise ValueError(f"op chain: unknown kind(s) {sorted(set(kinds[(kinds != np.floor(kinds)) | (kinds < 0) | (kinds >= AUG_KINDS)].tolist()))}")
+    rs = chain[:, :, 8][kinds == K_AFFINE]
+    if not np.all((rs == 2) | (rs == 3)):
+        raise ValueError("op chain: an affine op needs resample 2 (bilinear) or 3 (bicubic)")
+    return chain
+
+
 def collate_packed(batch, repeats: int = 1, size: int = 224):
     """Device-augment collate: the repeat re-ordering of ``collate_and_shuffle``, then windows
-    concatenated into one flat buffer with offsets written into the descriptors."""
+    concatenated into one flat buffer with offsets written into the descriptors; op chains
+    (``DeviceTrainParams``) stacked into one validated [B, slots, AUG_P] table."""
     batch = sum([batch[i::repeats] for i in range(repeats)], [])
     labels = None
-    if isinstance(batch[0][0], tuple):  # ((win, desc), label)
+    if isinstance(batch[0][0], tuple):  # ((win, desc[, chain]), label)
         labels = torch.tensor([b[1] for b in batch])
         batch = [b[0] for b in batch]
+    chain = None
+    if len(batch[0]) == 3:
+        chain = torch.from_numpy(check_chain(np.stack([b[2] for b in batch])))
+        batch = [b[:2] for b in batch]
     tab = np.stack([d for _, d in batch])
     sizes = np.array([w.size for w, _ in batch], dtype=np.int64)
     tab[:, 0] = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     rows = tab[:, 1]
     tab[:, 12] = np.concatenate([[0], np.cumsum(rows * size * 3)[:-1]])
     src = torch.from_numpy(np.concatenate([w.reshape(-1) for w, _ in batch]))
-    packed = PackedImages(src, torch.from_numpy(tab), int((rows * size * 3).sum()), int(rows.max()), size)
+    packed = PackedImages(src, torch.from_numpy(tab), int((rows * size * 3).sum()), int(rows.max()), size, chain)
     return packed if labels is None else (packed, labels)
 
 
 def unpack_on_device(p: PackedImages, device) -> torch.Tensor:
-    """uint8 [B, 3, S, S] from a packed batch: H2D of the windows, then the resize / flip kernels."""
+    """uint8 [B, 3, S, S] from a packed batch: H2D of the windows, then the resize / flip kernels
+    and, for a batch with an op chain, the chain kernels -- all on the current stream."""
     from ..ops import _ext
+    ext = _ext.load(True)
     src = p.src.to(device, non_blocking=True)
     tab = p.tab.to(device, non_blocking=True)
-    return _ext.load(True).rrc_resize(src, tab, p.size, p.tmp_bytes, p.rows_max)
+    out = ext.rrc_resize(src, tab, p.size, p.tmp_bytes, p.rows_max)
+    if p.chain is not None and p.chain.shape[1] > 0:
+        out = ext.aug_chain(out, p.chain.to(device, non_blocking=True), torch.empty_like(out))
+    return out
 
 
-def device_augment_ok(args) -> bool:
+def device_augment_rrc_only(args) -> bool:
     """The train transform is RandomResizedCrop + flip only (the pretraining presets)."""
     return (getattr(args, "random_crop", "rrc") == "rrc" and getattr(args, "auto_augment", "none") in ("none", "", None)
             and not getattr(args, "color_jitter", 0.0) and not getattr(args, "random_erasing", 0.0))
+
+
+def device_augment_ok(args) -> bool:
+    """The device augment covers the train transform: RandomResizedCrop + flip, optionally followed
+    by RandAugment (``rand-*``) or an AutoAugment policy and ColorJitter.  Not AugMix (parallel
+    chains), random erasing (np.random noise) or the ``src`` / ``none`` crops."""
+    from .autoaugment import POLICIES
+    aa = getattr(args, "auto_augment", "none") or "none"
+    return (getattr(args, "random_crop", "rrc") == "rrc" and not getattr(args, "random_erasing", 0.0)
+            and (aa == "none" or aa.startswith("rand") or aa.split("-")[0] in POLICIES))
 
 
 def repeat_samples(samples, repeats: int = 1):
@@ -296,8 +356,14 @@ def create_dataloaders(args, rank: int = 0, world: int = 1, start_batches: int =
     train_t, valid_t = create_transforms(args.random_crop, args.image_size, args.auto_augment, args.color_jitter,
                                          args.random_erasing, args.test_crop_ratio)
     if device_augment:
-        assert device_augment_ok(args), "device augment covers RandomResizedCrop + flip only"
-        train_t = DeviceRRCParams(args.image_size)
+        assert device_augment_ok(args), "device augment: AugMix, random erasing and src / none crops stay on the host"
+        if device_augment_rrc_only(args):
+            train_t = DeviceRRCParams(args.image_size)
+        else:
+            from .transforms import ColorJitter, auto_augment_factory
+            cj = args.color_jitter
+            train_t = DeviceTrainParams(args.image_size, auto_augment_factory(args.auto_augment or "none", args.image_size),
+                                        ColorJitter(cj, cj, cj) if cj > 0 else None)
     train_dl = valid_dl = None
     pin = torch.cuda.is_available()
     if getattr(args, "train_dataset_shards", None):

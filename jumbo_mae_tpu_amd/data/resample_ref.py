@@ -79,7 +79,11 @@ def unpack_packed(p) -> np.ndarray:
     for d in tab:
         n = int(d[1]) * int(d[2]) * 3
         outs.append(resize_window(src[int(d[0]):int(d[0]) + n], d, p.size))
-    return np.stack(outs)
+    out = np.stack(outs)
+    if getattr(p, "chain", None) is not None:  # RandAugment / AutoAugment / ColorJitter records
+        from .augment_ref import apply_chain
+        out = apply_chain(out, p.chain.numpy())
+    return out
 
 
 def taps(c: int, out: int) -> int:

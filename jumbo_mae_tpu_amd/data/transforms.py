@@ -135,6 +135,16 @@ class ColorJitter:
                 img = ImageEnhance.Color(img).enhance(f)
         return img
 
+    slots = property(lambda self: len(self.ops))
+
+    def describe(self, size: int) -> list:
+        """Op records of the device augment (data/autoaugment.py): __call__'s draws, no pixels."""
+        from .autoaugment import K_BRIGHTNESS, K_COLOR, K_CONTRAST, op_record
+        kinds = {"b": K_BRIGHTNESS, "c": K_CONTRAST, "s": K_COLOR}
+        ops = list(self.ops)
+        random.shuffle(ops)
+        return [op_record(kinds[name], random.uniform(lo, hi)) for name, lo, hi in ops]
+
 
 class PILToArray:
     """PIL -> uint8 CHW numpy array (PILToTensor)."""

@@ -103,8 +103,10 @@ def _extensions(p: argparse.ArgumentParser):
                         "jobs: continue with --resume auto); 0 = run to --training-steps")
     g.add_argument("--device", default=None, help="cuda|cpu (default: cuda if available)")
     g.add_argument("--device-augment", default="auto", choices=["auto", "on", "off"],
-                   help="RandomResizedCrop + flip of the train batches on the GPU, bit-exact to PIL (auto: on a GPU "
-                        "when the train transform is exactly that -- the pretraining presets)")
+                   help="train transform on the GPU, bit-exact to PIL: RandomResizedCrop + flip and, with 'on', "
+                        "RandAugment (rand-*) / AutoAugment policies / --color-jitter after it (auto: on a GPU when the "
+                        "train transform is RandomResizedCrop + flip only -- the pretraining presets; on: an error "
+                        "for AugMix, --random-erasing > 0 and --random-crop src|none, which stay on the host)")
     g.add_argument("--log-file-only", action="store_true", help="never use wandb even if installed")
     g.add_argument("--trace-ranges", action="store_true", help="roctx ranges per step phase (rocprofv3 --marker-trace)")
     g.add_argument("--hip-graph", action="store_true",

@@ -55,14 +55,18 @@ def make_reducer(args, store):
 
 
 def use_device_augment(args, device) -> bool:
-    """--device-augment: auto = on a GPU with the extension and the pretraining train transform."""
-    from ..data.loader import device_augment_ok
+    """--device-augment: auto = on a GPU with the extension and the pretraining train transform
+    (RandomResizedCrop + flip only); on = additionally RandAugment / AutoAugment / ColorJitter after
+    the crop (the finetune presets), and an error for what stays on the host."""
+    from ..data.loader import device_augment_ok, device_augment_rrc_only
     mode = getattr(args, "device_augment", "off")
     if mode == "off" or device.type != "cuda" or not getattr(args, "train_dataset_shards", None):
         return False
-    if not device_augment_ok(args):
-        if mode == "on":
-            raise SystemExit("--device-augment on: the train transform must be RandomResizedCrop + flip only")
+    if mode == "on" and not device_augment_ok(args):
+        raise SystemExit("--device-augment on: AugMix (--auto-augment augmix-*), --random-erasing > 0 and "
+                         "--random-crop src|none are not covered by the device augment; they run on the host "
+                         "(--device-augment off)")
+    if mode != "on" and not device_augment_rrc_only(args):
         return False
     from ..ops import _ext
     if not _ext.available():  # no built extension (JMAE_ALLOW_TORCH_FALLBACK runs): the PIL path

@@ -8,6 +8,12 @@ training rate.  Shards are written with real JPEG files at ImageNet-like sizes
 
     python tools/data_rate_bench.py [--workers 1,2,4,8] [--mode pretrain|finetune] [--batch 256]
                                     [--h2d] [--device-augment]
+                                    [--auto-augment SPEC] [--color-jitter X] [--random-erasing P]
+
+The augment flags override the mode's transform, so that the PIL and the device path can be
+measured per worker on one box with the same transform -- the config/ft.sh one is
+``--mode finetune --auto-augment rand-m9-mstd0.5-inc1 --color-jitter 0 --random-erasing 0``
+(``--device-augment`` then runs RandAugment on the GPU too, csrc/augment_chain.hip).
 
 Prints one JSON line per worker count: steady-state images/s of the loader (after draining what
 the workers prefetched), per worker, and with ``--h2d`` the rate through the DevicePrefetcher
@@ -31,11 +37,14 @@ from jumbo_mae_tpu_amd.data.jpeg_shards import write_shards  # noqa: E402
 from jumbo_mae_tpu_amd.data.loader import create_dataloaders  # noqa: E402
 
 
-def loader_args(spec: str, mode: str, batch: int, workers: int) -> SimpleNamespace:
+def loader_args(spec: str, mode: str, batch: int, workers: int, auto_augment=None, color_jitter=None,
+                random_erasing=None) -> SimpleNamespace:
     ft = mode == "finetune"
     return SimpleNamespace(
-        random_crop="rrc", image_size=224, auto_augment="rand-m9-mstd0.5-inc1" if ft else "none",
-        color_jitter=0.0, random_erasing=0.25 if ft else 0.0, test_crop_ratio=0.875,
+        random_crop="rrc", image_size=224,
+        auto_augment=auto_augment if auto_augment is not None else ("rand-m9-mstd0.5-inc1" if ft else "none"),
+        color_jitter=color_jitter if color_jitter is not None else 0.0,
+        random_erasing=random_erasing if random_erasing is not None else (0.25 if ft else 0.0), test_crop_ratio=0.875,
         train_dataset_shards=spec, valid_dataset_shards=None, mode=mode, train_batch_size=batch, grad_accum=1,
         augment_repeats=1, shuffle_seed=0, train_loader_workers=workers, valid_batch_size=batch,
         valid_loader_workers=0)
@@ -52,7 +61,11 @@ def main():
     ap.add_argument("--h2d", action="store_true", help="also through the DevicePrefetcher onto cuda:0")
     ap.add_argument("--device-augment", action="store_true",
                     help="workers decode + ship crop windows; resize / flip on the GPU (csrc/augment.hip)")
+    ap.add_argument("--auto-augment", default=None, help="train transform override (default: the mode's)")
+    ap.add_argument("--color-jitter", type=float, default=None)
+    ap.add_argument("--random-erasing", type=float, default=None)
     a = ap.parse_args()
+    aug = dict(auto_augment=a.auto_augment, color_jitter=a.color_jitter, random_erasing=a.random_erasing)
     spec = os.path.join(a.dir, f"train-{{000000..{a.shards - 1:06d}}}.tar")
     if not os.path.exists(os.path.join(a.dir, f"train-{a.shards - 1:06d}.tar")):
         t0 = time.time()
@@ -77,9 +90,13 @@ def main():
         return k * batch / (time.perf_counter() - t0), last
 
     for nw in [int(x) for x in a.workers.split(",")]:
-        dl, _ = create_dataloaders(loader_args(spec, a.mode, a.batch, nw), device_augment=a.device_augment)
+        largs = loader_args(spec, a.mode, a.batch, nw, **aug)
+        dl, _ = create_dataloaders(largs, device_augment=a.device_augment)
         rate, b = steady(iter(dl), nw, a.batch)
-        out = {"mode": a.mode, "device_augment": a.device_augment, "workers": nw, "images_per_sec": round(rate, 1),
+        b = b[0] if isinstance(b, (list, tuple)) else b  # finetune batches carry labels
+        out = {"mode": a.mode, "auto_augment": largs.auto_augment, "color_jitter": largs.color_jitter,
+               "random_erasing": largs.random_erasing,
+               "device_augment": a.device_augment, "workers": nw, "images_per_sec": round(rate, 1),
                "per_worker": round(rate / max(nw, 1), 1), "batch": a.batch, "jpeg_kb": round(mean_kb, 1),
                "cpus": os.cpu_count()}
         if a.device_augment:
@@ -88,7 +105,7 @@ def main():
         if a.h2d and torch.cuda.is_available():
             from jumbo_mae_tpu_amd.train.common import DevicePrefetcher
             dev = torch.device("cuda:0")
-            dl, _ = create_dataloaders(loader_args(spec, a.mode, a.batch, nw), device_augment=a.device_augment)
+            dl, _ = create_dataloaders(largs, device_augment=a.device_augment)
             rate, x = steady(DevicePrefetcher(dl, dev), nw, a.batch)
             out["prefetcher_images_per_sec"] = round(rate, 1)
             out["device_shape"] = list((x[0] if isinstance(x, (list, tuple)) else x).shape)

@@ -11,7 +11,13 @@ csrc/augment.hip) and the ``DevicePrefetcher`` side stream.  The driver logs ``p
 per log window (wall clock, host syncs included); the steady state is the mean over the windows
 after ``--skip`` steps.  Then ``bench.py --batch-per-gpu B`` on the same box.
 
+``--task finetune``: ``src/main_finetune.py`` with the config/ft.sh flags (ViT-B/16, RandAugment
+rand-m9-mstd0.5-inc1, mixup / cutmix) at 128 images per GPU (the per-GPU batch of the 8-GPU preset)
+against ``bench.py --task finetune`` at the same batch; ``--device-augment on|off`` selects the
+device train transform (csrc/augment.hip + augment_chain.hip) or PIL in the workers.
+
     python tools/product_rate.py --out gpurun_out/prod [--steps 60] [--batch 512] [--workers 8]
+                                 [--task pretrain|finetune] [--device-augment on|off]
     (under rocprofv3 --kernel-trace --memory-copy-trace: --driver-only, then tools/overlap_check.py)
 """
 
@@ -41,6 +47,16 @@ VITL = ["--mode", "pretrain", "--image_mask_ratio", "0.75", "--random-crop", "rr
         "--adam-eps", "1e-8", "--lr-decay", "1.0", "--clip-grad", "0.0", "--grad-accum", "1"]
 
 
+# config/ft.sh (ViT-B/16 finetune); schedule lengths are the preset's (global batch 1024)
+FT = ["--mode", "finetune", "--random-crop", "rrc", "--color-jitter", "0.0", "--auto-augment", "rand-m9-mstd0.5-inc1",
+      "--random-erasing", "0.0", "--augment-repeats", "1", "--test-crop-ratio", "0.875", "--mixup", "0.8",
+      "--cutmix", "1.0", "--criterion", "ce", "--label-smoothing", "0.1", "--layers", "12", "--dim", "768",
+      "--heads", "12", "--labels", "1000", "--patch-size", "16", "--image-size", "224", "--posemb", "sincos2d",
+      "--pooling", "cls", "--dropout", "0.0", "--droppath", "0.1", "--init-seed", "1", "--mixup-seed", "1",
+      "--dropout-seed", "1", "--shuffle-seed", "1", "--optimizer", "adamw", "--learning-rate", "3.0e-3",
+      "--weight-decay", "0.05", "--lr-decay", "0.75", "--clip-grad", "0.0", "--grad-accum", "1"]
+
+
 def _write_one(a):
     d, i, per_shard = a
     from jumbo_mae_tpu_amd.data.jpeg_shards import write_shards
@@ -61,9 +77,11 @@ def ensure_shards(d, shards, per_shard, procs):
 
 
 def driver_cmd(a, spec, out_dir):
-    return [sys.executable, "-u", os.path.join(ROOT, "src", "main_pretrain.py"), *VITL,
+    ft = a.task == "finetune"
+    return [sys.executable, "-u", os.path.join(ROOT, "src", "main_finetune.py" if ft else "main_pretrain.py"),
+            *(FT if ft else VITL),
             "--train-dataset-shards", spec, "--train-batch-size", str(a.batch), "--train-loader-workers",
-            str(a.workers), "--device-augment", "on", "--training-steps", str(a.steps), "--warmup-steps", "5",
+            str(a.workers), "--device-augment", a.device_augment, "--training-steps", str(a.steps), "--warmup-steps", "5",
             "--log-interval", str(a.log_interval), "--eval-interval", "0", "--output-dir", out_dir,
             "--name", "prod", "--log-file-only", "--device", "cuda"]
 
@@ -96,12 +114,15 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--skip", type=int, default=20, help="steps excluded from the steady state (warm-up, loader fill)")
     ap.add_argument("--log-interval", type=int, default=10)
-    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--task", default="pretrain", choices=["pretrain", "finetune"])
+    ap.add_argument("--device-augment", default="on", choices=["on", "off"])
+    ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: 512 pretrain, 128 finetune)")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--driver-only", action="store_true")
     ap.add_argument("--print-cmd", action="store_true",
                     help="write the shards, print the driver's argv (one per line, for rocprofv3 -- ...) and exit")
     a = ap.parse_args()
+    a.batch = a.batch or (128 if a.task == "finetune" else 512)
     os.makedirs(a.out, exist_ok=True)
     ensure_shards(a.shards_dir, a.shards, a.per_shard, a.procs)
     spec = os.path.join(a.shards_dir, f"train-{{000000..{a.shards - 1:06d}}}.tar")
@@ -110,14 +131,16 @@ def main():
     if a.print_cmd:
         print("\n".join(driver_cmd(a, spec, run_dir)))
         return
-    res = {"config": {"model": "ViT-L/16 jumbo-MAE (preset flags)", "per_gpu_batch": a.batch, "workers": a.workers,
-                      "steps": a.steps, "skip": a.skip, "device_augment": True, "cpus": os.cpu_count(),
+    model = "ViT-B/16 finetune (config/ft.sh flags)" if a.task == "finetune" else "ViT-L/16 jumbo-MAE (preset flags)"
+    res = {"config": {"model": model, "task": a.task, "per_gpu_batch": a.batch, "workers": a.workers,
+                      "steps": a.steps, "skip": a.skip, "device_augment": a.device_augment == "on",
+                      "cpus": os.cpu_count(),
                       "shards": f"{a.shards} x {a.per_shard} JPEG"}}
     res["driver"] = driver(a, spec, run_dir, os.path.join(a.out, "driver.log"))
     print(json.dumps({"driver": res["driver"]}), flush=True)
     if not a.driver_only:
         cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--batch-per-gpu", str(a.batch), "--steps", "30",
-               "--warmup", "5"]
+               "--warmup", "5", "--task", a.task]
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
         if r.returncode:
             raise SystemExit("bench failed:\n" + r.stderr[-2000:])
