@@ -21,6 +21,7 @@
 // Memory layout: qkv [B, S, 3, H, hd] (output of the fused QKV GEMM, read in place),
 // o / do [B, S, H, hd], lse [B, H, S] (natural log), dqkv [B, S, 3, H, hd].
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 

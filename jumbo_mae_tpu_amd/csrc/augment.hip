@@ -20,6 +20,7 @@
 // Per-image table (int64 x RRC_TAB): src offset, window rows / cols, window origin y0 / x0, image
 // H / W, crop i / j / h / w (PIL box (j, i, j + w, i + h)), flip, offset of its rows in tmp.
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 

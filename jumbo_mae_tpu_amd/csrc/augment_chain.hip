@@ -24,6 +24,7 @@
 // coefficients m0..m5, resample (2 bilinear, 3 bicubic), fill r, g, b.  A kind the device does not
 // know (the host rejects it in collate) is an identity copy, never an out-of-range access.
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 

@@ -6,133 +6,9 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-#include "jm_api.h"
+#include <climits>
 
-// ---- kernel entry points (see *.hip)
-int jm_layernorm_fwd(const float* x, long sB, long sT, int B, int T, int D, const float* gamma, const float* beta,
-                     float eps, void* y, int out_bf16, float* mean, float* rstd, hipStream_t st, uint16_t* y2 = nullptr);
-int jm_layernorm_bwd(const void* dy, int dy_bf16, const float* x, long sB, long sT, int B, int T, int D,
-                     const float* mean, const float* rstd, const float* gamma, float* dx_ptr, long oB, long oT,
-                     const float* dres, long rB, long rT, float* dgamma, float* dbeta, int accum_params, float* ws,
-                     const JmLnRes* res, hipStream_t st, const uint16_t* hx = nullptr,
-                     const float* beta = nullptr);
-int jm_layernorm_bwd_blocks(int rows, int D);
-// debug build (-DJM_DEBUG): first failing soft-check line per kernel translation unit (0 = none;
-// reading clears it); always 0 in the release build
-int jm_debug_line_attention();
-int jm_debug_line_dropout();
-int jm_debug_line_augment();
-int jm_rrc_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t* tmp, int tmp_rows_max, uint8_t* out,
-                  hipStream_t st);
-int jm_rrc_kmax();
-int jm_debug_line_augment_chain();
-int jm_aug_stat_words();
-int jm_aug_record_len();
-int jm_aug_chain(uint8_t* images, uint8_t* scratch, const double* chain, int B, int slots, int S, uint32_t* stats,
-                 hipStream_t st);
-int jm_dropout_apply(const void* x, void* y, long n, int bf16, const int64_t* seed, uint32_t thr, float scale,
-                     hipStream_t st);
-int jm_gelu_drop(const uint16_t* h, uint16_t* g, uint16_t* gp, long n, const int64_t* seed, uint32_t thr, float scale,
-                 hipStream_t st);
-int jm_softmax_dropout_fwd(const float* z, float* p, float* pd, long rows, int S, const int64_t* seed, uint32_t thr,
-                           float scale, hipStream_t st);
-int jm_softmax_dropout_bwd(const float* dpd, const float* p, float* dz, long rows, int S, const int64_t* seed,
-                           uint32_t thr, float scale, hipStream_t st);
-int jm_debug_line_elementwise();
-int jm_debug_line_gemm();
-int jm_debug_line_gemm_tn();
-int jm_debug_line_layernorm();
-int jm_debug_line_mae();
-int jm_debug_line_optim();
-void jm_debug_selftest(int v, hipStream_t st);
-int jm_residual_ln_fwd(const float* x, long sB, long sT, const uint16_t* y, const float* scale, const float* mask,
-                       float* x1, long oB, long oT, uint16_t* h, float* mean, float* rstd, int B, int T, int T0,
-                       int D, const float* gamma, const float* beta, float eps, hipStream_t st, int R0 = 0,
-                       JmDrop drop = JmDrop{nullptr, 0u, 1.f, 0});
-int jm_gelu_fwd(const uint16_t* h, uint16_t* a, long n, hipStream_t st);
-long jm_rowcol_ws_floats(int M, int N, int nacc);
-int jm_gelu_bwd(const uint16_t* h, const uint16_t* da, uint16_t* dh, float* bias_grad, int M, int N, hipStream_t st,
-                int deriv, float* ws);
-int jm_colsum_bf16(const uint16_t* x, float* acc, int M, int N, hipStream_t st, float* ws);
-int jm_splitk_reduce_add(const float* part, float* g, long n, int S, hipStream_t st, int store = 0);
-int jm_colsum_add_f32(const float* x, long ld, int rows, long n, float* g, hipStream_t st);
-int jm_zero_ranges(float* base, const long long* desc, int n, long long blocks, hipStream_t st);
-int jm_transpose_bf16(const uint16_t* src, uint16_t* dst, int R, int C, hipStream_t st);
-int jm_transpose_bf16_batch(const long long* desc, int n, int tiles, hipStream_t st);
-int jm_residual_fwd(const float* x, long sB, long sT, int B, int T, int D, const uint16_t* y, const float* scale,
-                    const float* mask, float* out, long oB, long oT, hipStream_t st, JmDrop drop);
-int jm_residual_bwd(const float* dout, long dB, long dT, const uint16_t* y, const float* scale, const float* mask,
-                    float* dscale, uint16_t* dy, int B, int T, int D, float* dbias, long yB, long yT, hipStream_t st,
-                    JmDrop drop, float* ws);
-int jm_attn_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int H, int hd, const int64_t* dseed,
-                uint32_t dthr, float dscale, hipStream_t st);
-int jm_attn_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv, int B,
-                int S, int H, int hd, float* dbias_part, const int64_t* dseed, uint32_t dthr, float dscale,
-                hipStream_t st);
-int jm_attn_max_seq();
-int jm_attn_head_dims(const int** dims);
-int jm_attn_tiled(int S, int hd);
-int jm_attn_fused_bias(int S, int hd);
-int jm_attn_bwd_part_rows(int B, int S, int hd);
-int jm_attn_bwd_long(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv,
-                     float* delta, int B, int S, int H, int hd, const int64_t* dseed, uint32_t dthr, float dscale,
-                     hipStream_t st);
-int jm_attn_dropout(int S, int hd);
-void jm_opt_sumsq(const float* x, const int* chunks, int nchunks, float* out, float* cpart, hipStream_t st);
-void jm_zero_f32(float* p, long n, hipStream_t st);
-void jm_opt_adamw(float* p, const float* g, float* mu, float* nu, uint16_t* shadow, const int* chunks, int nchunks,
-                  const float* meta, const float* hyper, const float* gnorm_sq, hipStream_t st);
-void jm_opt_lamb_phase1(const float* p, const float* g, float* mu, float* nu, float* u, const int* chunks, int nchunks,
-                        const float* meta, const float* hyper, const float* gnorm_sq, float* norms, float* cpart,
-                        hipStream_t st);
-void jm_opt_lars_norms(const float* p, const float* g, const int* chunks, int nchunks, const float* hyper,
-                       const float* gnorm_sq, float* norms, float* cpart, hipStream_t st);
-void jm_opt_apply_trust(float* p, const float* u_or_g, float* trace, uint16_t* shadow, const int* chunks, int nchunks,
-                        const float* meta, const float* hyper, const float* norms, const float* gnorm_sq, int mode,
-                        float momentum, float trust_coef, hipStream_t st);
-void jm_opt_sgd(float* p, const float* g, float* trace, uint16_t* shadow, const int* chunks, int nchunks,
-                const float* meta, const float* hyper, const float* gnorm_sq, float momentum, hipStream_t st);
-int jm_splitk_reduce_bf16(const float* part, int S, long n, int N, const float* bias, uint16_t* out, hipStream_t st);
-int jm_splitk_reduce_f32(const float* part, int S, int M, int N, const float* bias, const float* add, long add_ld,
-                         float* out, hipStream_t st);
-int jm_gemm_nt(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int epi,
-               const GemmEpi& ep, hipStream_t st);
-int jm_gemm_nt_tiles(int M, int N, int K, int epi, long lda);
-int jm_gemm_nt_colpart_rows(int M, int N, int K, int epi, long lda);
-int jm_gemm_nt_tail_plan(int M, int N, int K, int epi, long lda, int* tail_r, long* ws_floats);
-void jm_gemm_test_force(int path, int rows);
-int jm_gemm_tn_plan(int M, int N, int K, int* S_out);
-int jm_gemm_tn_group_plan(const TnGroup& grp, int M, int* S_out);
-int jm_gemm_tn_group(TnGroup grp, int M, int sps, int S, hipStream_t st, int store);
-int jm_gemm_tn(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int sps, int S,
-               float* G, long ldo, float* partial, hipStream_t st, int store);
-struct TnSegs {  // gemm_tn.hip layout
-  const uint16_t* a[64];
-  const uint16_t* b[64];
-  int rows;
-  int n;
-};
-int jm_gemm_tn_group_seg(TnGroup grp, const TnSegs& segs, int sps, int S, hipStream_t st, int store);
-int jm_gemm_tn_seg(const TnSegs& segs, long lda, long ldb, int N, int K, int sps, int S, float* G, long ldo,
-                   float* partial, hipStream_t st, int store);
-int jm_patchify_normalize(const uint8_t* img, float* out, int B, int H, int W, int p, hipStream_t st);
-int jm_gather_patches(const uint8_t* img, const int* ids, long idsB, uint16_t* out, int B, int K, int H, int W, int p,
-                      hipStream_t st);
-int jm_embed_finish(const uint16_t* e, const float* pos, const int* ids, long idsB, const float* cls, float* out,
-                    int B, int C, int K, int D, hipStream_t st);
-int jm_mask_ids(const float* noise, int R, int N, int keep, int64_t* shuffle, int64_t* restore, int* keep32,
-                int* restore32, float* mask, hipStream_t st);
-int jm_unshuffle_fwd(const uint16_t* y, const float* tok, const int* restore, long rsB, const float* pos, float* out,
-                     int B, int C, int K, int N, int d, hipStream_t st);
-int jm_unshuffle_bwd_blocks(int B, int C, int N, int rows_per_block);
-int jm_unshuffle_bwd(const float* dout, const int* restore, long rsB, uint16_t* dy, float* part, int B, int C, int K,
-                     int N, int d, int rows_per_block, hipStream_t st);
-int jm_mix_patches(const uint8_t* img, const int* perm, const float* prm, const int* box, uint16_t* out, int B, int H,
-                   int W, int p, hipStream_t st);
-int jm_patch_mse_fwd(const uint16_t* pred, long ldp, const uint8_t* img, float* mse, long rows, int N, int H, int W,
-                     int p, int norm_pix, hipStream_t st);
-int jm_patch_mse_bwd(const uint16_t* pred, long ldp, const uint8_t* img, const float* dmse, uint16_t* dpred, long rows,
-                     int N, int H, int W, int p, int norm_pix, hipStream_t st);
+#include "jm_api.h"
 
 namespace {
 
@@ -1041,75 +917,13 @@ void transpose_bf16_batch(torch::Tensor desc, int64_t tiles) {
            "transpose_bf16_batch");
 }
 
-// weight gradient G[N, K] += dy[M, N]^T . x[M, K] on the TN MFMA kernel (split over M, fp32
-// partial tiles reduced into G); returns the number of M splits used
-// store: g = dy^T . x (g's old contents ignored: its first contribution of the step)
-int64_t gemm_tn_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor g, bool store) {
-  CHECK_DT(dy, torch::kBFloat16);
-  CHECK_DT(x, torch::kBFloat16);
-  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0), "gemm_tn_wgrad: dy [M,N], x [M,K]");
-  TORCH_CHECK(dy.stride(1) == 1 && x.stride(1) == 1, "gemm_tn_wgrad: rows must be contiguous");
-  const int M = dy.size(0), N = dy.size(1), K = x.size(1);
-  TORCH_CHECK(g.is_contiguous() && g.scalar_type() == torch::kFloat32 && g.numel() == (long)N * K, "gemm_tn_wgrad g");
-  int S = 1;
-  const int sps = jm_gemm_tn_plan(M, N, K, &S);
-  torch::Tensor part;
-  const int SP = S;  // fp32 partial slices, reduced into g
-  if (S > 1) part = torch::empty({SP, (long)N * K}, g.options());
-  const int done = jm_gemm_tn(bf(dy), dy.stride(0), bf(x), x.stride(0), M, N, K, sps, S, g.data_ptr<float>(), K,
-                              S > 1 ? part.data_ptr<float>() : nullptr, stream(), store);
-  check_rc(done, "gemm_tn_wgrad");
-  if (S > 1)
-    check_rc(jm_splitk_reduce_add(part.data_ptr<float>(), g.data_ptr<float>(), (long)N * K, SP, stream(), store),
-             "gemm_tn_wgrad reduce");
-  return S;
-}
+// ------------------------------------------------------------------------------ weight gradients
+using Tensors = std::vector<torch::Tensor>;
 
-// g[N, K] += sum_i dys[i]^T xs[i]: the reduction rows are the concatenation of the per-layer
-// blocks (all [rows, N] / [rows, K], same strides), read in place (no torch.cat copy)
-int64_t gemm_tn_wgrad_seg(std::vector<torch::Tensor> dys, std::vector<torch::Tensor> xs, torch::Tensor g, bool store) {
-  TORCH_CHECK(!dys.empty() && dys.size() == xs.size() && dys.size() <= 32, "gemm_tn_wgrad_seg: 1..32 blocks");
-  const auto& d0 = dys[0];
-  const auto& x0 = xs[0];
-  const int rows = d0.size(0), N = d0.size(1), K = x0.size(1);
-  TnSegs segs{};
-  segs.rows = rows;
-  segs.n = (int)dys.size();
-  for (size_t i = 0; i < dys.size(); ++i) {
-    CHECK_DT(dys[i], torch::kBFloat16);
-    CHECK_DT(xs[i], torch::kBFloat16);
-    TORCH_CHECK(dys[i].dim() == 2 && xs[i].dim() == 2 && dys[i].size(0) == rows && xs[i].size(0) == rows &&
-                    dys[i].size(1) == N && xs[i].size(1) == K,
-                "gemm_tn_wgrad_seg: block shapes differ");
-    TORCH_CHECK(dys[i].stride(1) == 1 && xs[i].stride(1) == 1 && dys[i].stride(0) == d0.stride(0) &&
-                    xs[i].stride(0) == x0.stride(0),
-                "gemm_tn_wgrad_seg: block strides differ");
-    segs.a[i] = bf(dys[i]);
-    segs.b[i] = bf(xs[i]);
-  }
-  TORCH_CHECK(g.is_contiguous() && g.scalar_type() == torch::kFloat32 && g.numel() == (long)N * K, "gemm_tn_wgrad_seg g");
-  const int M = rows * segs.n;
-  int S = 1;
-  const int sps = jm_gemm_tn_plan(M, N, K, &S);
-  torch::Tensor part;
-  const int SP = S;
-  if (S > 1) part = torch::empty({SP, (long)N * K}, g.options());
-  const int done = jm_gemm_tn_seg(segs, d0.stride(0), x0.stride(0), N, K, sps, S, g.data_ptr<float>(), K,
-                                  S > 1 ? part.data_ptr<float>() : nullptr, stream(), store);
-  check_rc(done, "gemm_tn_wgrad_seg");
-  if (S > 1)
-    check_rc(jm_splitk_reduce_add(part.data_ptr<float>(), g.data_ptr<float>(), (long)N * K, SP, stream(), store),
-             "gemm_tn_wgrad_seg reduce");
-  return S;
-}
-
-// g_p[N_p, K_p] += dys[p]^T . xs[p] for up to 4 problems over the same M rows in ONE grid (e.g. a
-// layer's FF1 + FF2 or QKV + Wo weight gradients): fewer M splits per problem than separate
-// launches -> fewer fp32 partial slices to write and reduce; returns the split count
 // One-split grouped launches store into every G or accumulate into every G (one kernel variant):
 // with mixed store flags the store problems' G are zeroed first and all accumulate.  Returns the
 // launch's store mode.
-int group_stores(const std::vector<bool>& stores, const std::vector<torch::Tensor>& gs, int S, int n) {
+int group_stores(const std::vector<bool>& stores, const Tensors& gs, int S, int n) {
   if (S > 1 || stores.empty()) return 0;
   int ns = 0;
   for (int p = 0; p < n; ++p) ns += p < (int)stores.size() && stores[p];
@@ -1120,109 +934,103 @@ int group_stores(const std::vector<bool>& stores, const std::vector<torch::Tenso
   return 0;
 }
 
-// stores[p]: g_p = its product (first contribution of the step) instead of +=
-int64_t gemm_tn_wgrad_group(std::vector<torch::Tensor> dys, std::vector<torch::Tensor> xs,
-                            std::vector<torch::Tensor> gs, std::vector<bool> stores) {
-  const int n = (int)dys.size();
-  TORCH_CHECK(n >= 1 && n <= 4 && (int)xs.size() == n && (int)gs.size() == n, "gemm_tn_wgrad_group: 1..4 problems");
-  const int M = dys[0].size(0);
-  TnGroup grp{};
-  grp.n = n;
-  long total = 0;
-  for (int p = 0; p < n; ++p) {
-    const auto &dy = dys[p], &x = xs[p], &g = gs[p];
-    CHECK_DT(dy, torch::kBFloat16);
-    CHECK_DT(x, torch::kBFloat16);
-    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == M && x.size(0) == M,
-                "gemm_tn_wgrad_group: dy [M,N_p], x [M,K_p] with one M");
-    TORCH_CHECK(dy.stride(1) == 1 && x.stride(1) == 1, "gemm_tn_wgrad_group: rows must be contiguous");
-    const int N = dy.size(1), K = x.size(1);
-    TORCH_CHECK(N % 256 == 0 && K % 256 == 0, "gemm_tn_wgrad_group: N, K multiples of 256");
-    TORCH_CHECK(g.is_contiguous() && g.scalar_type() == torch::kFloat32 && g.numel() == (long)N * K && g.is_cuda(),
-                "gemm_tn_wgrad_group g");
-    grp.a[p] = bf(dy);
-    grp.b[p] = bf(x);
-    grp.lda[p] = dy.stride(0);
-    grp.ldb[p] = x.stride(0);
-    grp.N[p] = N;
-    grp.K[p] = K;
-    total += (long)N * K;
-  }
-  int S = 1;
-  const int sps = jm_gemm_tn_group_plan(grp, M, &S);
-  torch::Tensor part;
-  long off = 0;
-  if (S > 1) part = torch::empty({(long)S * total}, gs[0].options());
-  for (int p = 0; p < n; ++p) {
-    grp.out[p] = S > 1 ? part.data_ptr<float>() + off : gs[p].data_ptr<float>();
-    off += (long)S * grp.N[p] * grp.K[p];
-  }
-  const int all_store = group_stores(stores, gs, S, n);
-  check_rc(jm_gemm_tn_group(grp, M, sps, S, stream(), all_store), "gemm_tn_wgrad_group");
-  if (S > 1)
-    for (int p = 0; p < n; ++p)
-      check_rc(jm_splitk_reduce_add(grp.out[p], gs[p].data_ptr<float>(), (long)grp.N[p] * grp.K[p], S, stream(),
-                                    p < (int)stores.size() && stores[p]),
-               "gemm_tn_wgrad_group reduce");
-  return S;
-}
-
-// g_p[N_p, K_p] += sum_i dys[p][i]^T xs[p][i] for two problems whose reduction rows are the same
-// per-layer blocks (the shared jumbo MLP's W1 and W2 gradients over all layers), one grid
-int64_t gemm_tn_wgrad_seg_group(std::vector<std::vector<torch::Tensor>> dys, std::vector<std::vector<torch::Tensor>> xs,
-                                std::vector<torch::Tensor> gs, std::vector<bool> stores) {
-  const int np = (int)dys.size();
-  TORCH_CHECK(np >= 1 && np <= 2 && (int)xs.size() == np && (int)gs.size() == np, "gemm_tn_wgrad_seg_group: 1-2 problems");
+// gs[p] [N_p, K_p] += sum_i dys[p][i]^T . xs[p][i] on the TN MFMA kernels (csrc/gemm_tn.hip): up to
+// 4 problems over the same M rows in ONE grid (fewer M splits per problem than separate launches,
+// so fewer fp32 partial slices to write and reduce), the M rows split over S workgroups per tile
+// and the partial slices reduced into gs[p]; returns S.  segmented: the M rows of each problem are
+// its 1..32 row blocks (same shape and strides), read in place -- no torch.cat copy -- for at most
+// 2 problems; else one block per problem.  stores[p]: gs[p] = the product (its old contents
+// ignored: the first contribution of a step) instead of +=.
+int64_t tn_wgrad(const char* what, const std::vector<Tensors>& dys, const std::vector<Tensors>& xs, const Tensors& gs,
+                 const std::vector<bool>& stores, bool segmented) {
+  const int np = (int)dys.size(), max_np = segmented ? 2 : 4, max_nb = segmented ? 32 : 1;
+  TORCH_CHECK(np >= 1 && np <= max_np && (int)xs.size() == np && (int)gs.size() == np, what, ": 1..", max_np,
+              " problems, each with its dy, x and g");
   const int nb = (int)dys[0].size();
-  TORCH_CHECK(nb >= 1 && nb <= 32, "gemm_tn_wgrad_seg_group: 1..32 blocks");
-  const int rows = dys[0][0].size(0);
-  TnSegs segs{};
-  segs.rows = rows;
-  segs.n = nb;
+  TORCH_CHECK(nb >= 1 && nb <= max_nb, what, ": 1..", max_nb, " row blocks");
+  const auto dev = gs[0].device();
+  TORCH_CHECK(dev.is_cuda(), what, ": g must be a GPU tensor");
   TnGroup grp{};
+  TnSegs segs{};
   grp.n = np;
-  long total = 0;
+  int64_t rows = -1, total = 0;
   for (int p = 0; p < np; ++p) {
-    TORCH_CHECK((int)dys[p].size() == nb && (int)xs[p].size() == nb, "gemm_tn_wgrad_seg_group: block counts differ");
+    TORCH_CHECK((int)dys[p].size() == nb && (int)xs[p].size() == nb, what, ": block counts differ");
     const auto &d0 = dys[p][0], &x0 = xs[p][0];
-    const int N = d0.size(1), K = x0.size(1);
     for (int i = 0; i < nb; ++i) {
       const auto &d = dys[p][i], &x = xs[p][i];
-      CHECK_DT(d, torch::kBFloat16);
-      CHECK_DT(x, torch::kBFloat16);
-      TORCH_CHECK(d.dim() == 2 && x.dim() == 2 && d.size(0) == rows && x.size(0) == rows && d.size(1) == N &&
-                      x.size(1) == K && d.stride(1) == 1 && x.stride(1) == 1 && d.stride(0) == d0.stride(0) &&
+      TORCH_CHECK(d.scalar_type() == torch::kBFloat16 && x.scalar_type() == torch::kBFloat16, what,
+                  ": dy and x must be bf16");
+      TORCH_CHECK(d.device() == dev && x.device() == dev, what, ": dy and x must be on g's GPU");
+      TORCH_CHECK(d.dim() == 2 && x.dim() == 2 && d.stride(1) == 1 && x.stride(1) == 1, what,
+                  ": dy [M,N], x [M,K] with contiguous rows");
+      if (rows < 0) rows = d.size(0);
+      TORCH_CHECK(d.size(0) == rows && x.size(0) == rows, what, ": dy and x of every problem and block have one M");
+      TORCH_CHECK(d.size(1) == d0.size(1) && x.size(1) == x0.size(1) && d.stride(0) == d0.stride(0) &&
                       x.stride(0) == x0.stride(0),
-                  "gemm_tn_wgrad_seg_group: block shapes / strides differ");
-      segs.a[32 * p + i] = bf(d);
-      segs.b[32 * p + i] = bf(x);
+                  what, ": block shapes / strides differ");
+      if (segmented) {
+        segs.a[32 * p + i] = bf(d);
+        segs.b[32 * p + i] = bf(x);
+      }
     }
+    const int64_t N = d0.size(1), K = x0.size(1);
+    TORCH_CHECK(N > 0 && K > 0 && N % 256 == 0 && K % 256 == 0, what, ": N, K multiples of 256");
     const auto& g = gs[p];
-    TORCH_CHECK(g.is_contiguous() && g.scalar_type() == torch::kFloat32 && g.numel() == (long)N * K,
-                "gemm_tn_wgrad_seg_group g");
+    TORCH_CHECK(g.device() == dev && g.scalar_type() == torch::kFloat32 && g.is_contiguous() && g.numel() == N * K,
+                what, ": g must be fp32 [N,K], contiguous, on one GPU");
+    if (!segmented) {
+      grp.a[p] = bf(d0);
+      grp.b[p] = bf(x0);
+    }
     grp.lda[p] = d0.stride(0);
     grp.ldb[p] = x0.stride(0);
-    grp.N[p] = N;
-    grp.K[p] = K;
-    total += (long)N * K;
+    grp.N[p] = (int)N;
+    grp.K[p] = (int)K;
+    total += N * K;
   }
+  TORCH_CHECK(rows >= 1 && rows * nb <= INT_MAX, what, ": M out of range");
+  const int M = (int)(rows * nb);
+  segs.rows = (int)rows;
+  segs.n = nb;
   int S = 1;
-  const int sps = jm_gemm_tn_group_plan(grp, rows * nb, &S);
-  torch::Tensor part;
-  if (S > 1) part = torch::empty({(long)S * total}, gs[0].options());
-  long off = 0;
+  const int sps = jm_gemm_tn_plan(grp, M, &S);
+  torch::Tensor part;  // fp32 partial slices [S][N_p K_p] per problem, reduced into gs[p]
+  if (S > 1) part = torch::empty({S * total}, gs[0].options());
+  int64_t off = 0;
   for (int p = 0; p < np; ++p) {
     grp.out[p] = S > 1 ? part.data_ptr<float>() + off : gs[p].data_ptr<float>();
-    off += (long)S * grp.N[p] * grp.K[p];
+    off += (int64_t)S * grp.N[p] * grp.K[p];
   }
   const int all_store = group_stores(stores, gs, S, np);
-  check_rc(jm_gemm_tn_group_seg(grp, segs, sps, S, stream(), all_store), "gemm_tn_wgrad_seg_group");
+  check_rc(jm_gemm_tn(grp, segmented ? &segs : nullptr, M, sps, S, stream(), all_store), what);
   if (S > 1)
     for (int p = 0; p < np; ++p)
       check_rc(jm_splitk_reduce_add(grp.out[p], gs[p].data_ptr<float>(), (long)grp.N[p] * grp.K[p], S, stream(),
                                     p < (int)stores.size() && stores[p]),
-               "gemm_tn_wgrad_seg_group reduce");
+               what);
   return S;
+}
+
+// the Python-visible forms: one problem or several, contiguous rows or row blocks
+int64_t gemm_tn_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor g, bool store) {
+  return tn_wgrad("gemm_tn_wgrad", {Tensors{dy}}, {Tensors{x}}, {g}, {store}, false);
+}
+
+int64_t gemm_tn_wgrad_seg(Tensors dys, Tensors xs, torch::Tensor g, bool store) {
+  return tn_wgrad("gemm_tn_wgrad_seg", {dys}, {xs}, {g}, {store}, true);
+}
+
+int64_t gemm_tn_wgrad_group(Tensors dys, Tensors xs, Tensors gs, std::vector<bool> stores) {
+  std::vector<Tensors> d, x;
+  for (const auto& t : dys) d.push_back({t});
+  for (const auto& t : xs) x.push_back({t});
+  return tn_wgrad("gemm_tn_wgrad_group", d, x, gs, stores, false);
+}
+
+int64_t gemm_tn_wgrad_seg_group(std::vector<Tensors> dys, std::vector<Tensors> xs, Tensors gs,
+                                std::vector<bool> stores) {
+  return tn_wgrad("gemm_tn_wgrad_seg_group", dys, xs, gs, stores, true);
 }
 
 // zero the (offset, count) float ranges of ``base`` listed in desc (int64 [n, 2] on the device)

@@ -109,13 +109,10 @@ def build_io(verbose: bool = True) -> Path:
 FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-fno-slp-vectorize"]}
 
 
-def build(jobs: int = 8, verbose: bool = True, clean: bool = False, variant: str = "release") -> Path:
-    if clean and BUILD.exists():
-        shutil.rmtree(BUILD)
-    BUILD.mkdir(parents=True, exist_ok=True)
+def _flags(variant: str, src_dir: Path = HERE):
+    """(kernel flags, bindings flags, link flags, torch's library directory) of a variant."""
     incs, torch_lib, abi = _torch_paths()
-    hdrs = sorted(HERE.glob("*.h"))
-    kflags = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-I" + str(HERE),
+    kflags = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-I" + str(src_dir),
               "-munsafe-fp-atomics", "-Wno-unused-result"]
     name = VARIANTS[variant]
     cflags = ["-O2", "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
@@ -133,20 +130,36 @@ def build(jobs: int = 8, verbose: bool = True, clean: bool = False, variant: str
         cflags += ["-fsanitize=address", "-fsanitize=undefined", "-fno-omit-frame-pointer", "-g"]
         ubsan = subprocess.run(["gcc", "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
         lflags += [ubsan]
+    return kflags, cflags, lflags, torch_lib
 
+
+def plan(variant: str = "release", src_dir: Path = HERE, out_dir: Path = BUILD) -> list:
+    """The objects of a variant and the commands that make them, ``[(object path, command)]`` (the
+    kernel files, then the bindings); runs nothing.  An object's name carries the hash of its
+    source, of EVERY header (jm_api.h is the interface between the bindings and the kernels: an
+    object cached from before a header edit must never be linked) and of its flags."""
+    kflags, cflags, _, _ = _flags(variant, src_dir)
+    hdrs = sorted(src_dir.glob("*.h"))
     jobs_list = []
     for k in KERNELS:
-        src = HERE / k
+        src = src_dir / k
         if not src.exists():
             continue
         fl = kflags + FILE_FLAGS.get(k, [])
-        dig = _digest([src] + hdrs, fl)
-        obj = BUILD / f"{src.stem}.{dig}.o"
+        obj = out_dir / f"{src.stem}.{_digest([src] + hdrs, fl)}.o"
         jobs_list.append((obj, [HIPCC] + fl + ["-c", str(src), "-o", str(obj)]))
-    bsrc = HERE / "bindings.cpp"
-    dig = _digest([bsrc], cflags)
-    bobj = BUILD / f"bindings.{dig}.o"
+    bsrc = src_dir / "bindings.cpp"
+    bobj = out_dir / f"bindings.{_digest([bsrc] + hdrs, cflags)}.o"
     jobs_list.append((bobj, ["g++"] + cflags + ["-c", str(bsrc), "-o", str(bobj)]))
+    return jobs_list
+
+
+def build(jobs: int = 8, verbose: bool = True, clean: bool = False, variant: str = "release") -> Path:
+    if clean and BUILD.exists():
+        shutil.rmtree(BUILD)
+    BUILD.mkdir(parents=True, exist_ok=True)
+    _, _, lflags, torch_lib = _flags(variant)
+    jobs_list = plan(variant)
 
     todo = [(o, c) for o, c in jobs_list if not o.exists()]
     if verbose and todo:

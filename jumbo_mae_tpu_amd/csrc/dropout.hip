@@ -16,6 +16,7 @@
 // tests' oracle).  Attention probabilities [rows = (b h, q), S] index their mask transposed,
 // ((b h) S + c) SE + q with SE = S rounded up to even (the fused attention kernels' convention).
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 

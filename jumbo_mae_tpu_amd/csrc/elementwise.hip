@@ -13,6 +13,7 @@
 // adds the partial rows into the fp32 grad buffer in a fixed order (no float atomics: the same
 // bits on every run).
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 
@@ -313,7 +314,6 @@ int jm_residual_bwd(const float* dout, long dB, long dT, const uint16_t* y, cons
 
 // ---------------------------------------------------------------------------------------------
 // Split-K epilogue of the weight-gradient GEMMs: g[i] += sum_s part[s][i] (fp32), one pass.
-void jm_zero_f32(float* p, long n, hipStream_t st);
 namespace {
 // g[i] += sum_s part[s][i], one thread per float4 column walking all S rows (n large).
 // ``ld``: row stride of part in floats (n for the packed partial slices, a strided view otherwise).

@@ -110,30 +110,18 @@ struct TFrags {
   bf16x8_t b[4], a[8];
 };
 
-}  // namespace
-
-// Segmented M (the batched shared-jumbo-MLP weight gradient): the reduction rows are the
-// concatenation of ``n`` separately allocated [rows, lda] / [rows, ldb] blocks (one per layer),
-// read in place instead of being copied into one tensor first.
-// A grouped segmented launch (jm_gemm_tn_group_seg) keeps problem p's blocks at entries 32 p + i.
-struct TnSegs {
-  const uint16_t* a[64];
-  const uint16_t* b[64];
-  int rows;  // rows per block, multiple of the 32-row step
-  int n;
-};
-
-namespace {
-
+// The 32-row-step kernel, kept for segmented M (jm_api.h TnSegs) whose blocks are no multiple of
+// the 4-phase kernel's 64 rows; every other launch runs gemm_tn4_kernel below.  A and B are unused
+// (the rows come from segs).
 // ACC = 1: G += tile (S == 1), 0: store the fp32 partial tile of split s into slice s.  (Split 0
 // adding straight into G measured slower -- the read-modify-write exposes a load latency in the
 // epilogue, profiles/r1_ab_tn_acc0.txt -- and so did float-atomic split reduction,
 // profiles/r2_tn_atomic.txt; both removed.)
-template <int ACC, bool SEG = false>
+template <int ACC>
 __global__ __launch_bounds__(NTH, 1) void gemm_tn_kernel(const uint16_t* __restrict__ A, long lda,
                                                          const uint16_t* __restrict__ B, long ldb, int M, int N,
                                                          int K, int steps_per_split, float* __restrict__ out,
-                                                         long ldo, long split_stride, TnSegs segs = {}) {
+                                                         long ldo, long split_stride, TnSegs segs) {
   JM_DGUARD(blockDim.x == NTH && steps_per_split >= 1 && M > 0);
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   const int tid = threadIdx.x;
@@ -156,8 +144,6 @@ __global__ __launch_bounds__(NTH, 1) void gemm_tn_kernel(const uint16_t* __restr
   nk += nk & 1;  // even: the pipeline runs in pairs; rows past the split read zeros
   if (nk < 2) nk = 2;
 
-  const __amdgpu_buffer_rsrc_t ra = make_rsrc(SEG ? segs.a[0] : A + (long)m_begin * lda + n0, SEG ? 0 : (long)rows * lda * 2);
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(SEG ? segs.b[0] : B + (long)m_begin * ldb + k0, SEG ? 0 : (long)rows * ldb * 2);
   // staging: each wave-instruction moves 2 rows x 512 B; 16 per operand and stage -> 2 rounds
   uint32_t a_src[2], b_src[2];
 #pragma unroll
@@ -170,25 +156,17 @@ __global__ __launch_bounds__(NTH, 1) void gemm_tn_kernel(const uint16_t* __restr
   auto issue = [&](int t) {
     uint16_t* la = smem + (t % NST) * STAGE;
     uint16_t* lb = la + BS * TN_;
-    if constexpr (SEG) {  // this step's 32 rows lie in one block; past the split: empty range (zeros)
-      const int row = m_begin + t * BS;
-      const int sg = min(row / segs.rows, segs.n - 1);
-      const int loc = row - sg * segs.rows;
-      const int left = row < m_begin + rows ? min(segs.rows - loc, m_begin + rows - row) : 0;
-      const __amdgpu_buffer_rsrc_t sra = make_rsrc(segs.a[sg] + (long)loc * lda + n0, (long)left * lda * 2);
-      const __amdgpu_buffer_rsrc_t srb = make_rsrc(segs.b[sg] + (long)loc * ldb + k0, (long)left * ldb * 2);
+    // this step's 32 rows lie in one block; past the split: empty range (zeros)
+    const int row = m_begin + t * BS;
+    const int sg = min(row / segs.rows, segs.n - 1);
+    const int loc = row - sg * segs.rows;
+    const int left = row < m_begin + rows ? min(segs.rows - loc, m_begin + rows - row) : 0;
+    const __amdgpu_buffer_rsrc_t sra = make_rsrc(segs.a[sg] + (long)loc * lda + n0, (long)left * lda * 2);
+    const __amdgpu_buffer_rsrc_t srb = make_rsrc(segs.b[sg] + (long)loc * ldb + k0, (long)left * ldb * 2);
 #pragma unroll
-      for (int rr = 0; rr < 2; ++rr) {
-        blds16(sra, a_src[rr], 0, la + (rr * 16 + wave * 2) * TN_);
-        blds16(srb, b_src[rr], 0, lb + (rr * 16 + wave * 2) * TK_);
-      }
-    } else {
-      const uint32_t sa = (uint32_t)(t * BS * lda * 2), sb = (uint32_t)(t * BS * ldb * 2);
-#pragma unroll
-      for (int rr = 0; rr < 2; ++rr) {
-        blds16(ra, a_src[rr], sa, la + (rr * 16 + wave * 2) * TN_);
-        blds16(rb, b_src[rr], sb, lb + (rr * 16 + wave * 2) * TK_);
-      }
+    for (int rr = 0; rr < 2; ++rr) {
+      blds16(sra, a_src[rr], 0, la + (rr * 16 + wave * 2) * TN_);
+      blds16(srb, b_src[rr], 0, lb + (rr * 16 + wave * 2) * TK_);
     }
   };
   // transposing fragment reads: rows 8g + l16/4 (+4), columns base + 4 (l16 & 3)
@@ -556,16 +534,23 @@ __global__ __launch_bounds__(NTH, 1) void gemm_tn4_kernel(const uint16_t* __rest
 
 size_t jm_gemm_tn_smem() { return (size_t)NST * STAGE * sizeof(uint16_t); }
 
-// Split of the M range: returns steps (of 32 rows) per split; *S_out = number of splits.
+// Split of the M range over the tiles and output elements of all of grp's problems together:
+// returns steps (of 32 rows) per split -- whole 128-row units of the 4-phase kernel, so a multiple
+// of 4 and >= 4 for every M >= 1; *S_out = number of splits.
 // Picks the split count that minimises an estimate of (waves of 256 CUs) x (steps per split +
 // epilogue) + the fp32 partial-tile traffic of the reduction (weight A/B: profiles/r2_tn_plan_scale.txt).
-namespace {
-int tn_plan(int M, int tiles, long NK, int* S_out) {
+int jm_gemm_tn_plan(const TnGroup& grp, int M, int* S_out) {
+  long NK = 0;
+  int tiles = 0;
+  for (int p = 0; p < grp.n; ++p) {
+    NK += (long)grp.N[p] * grp.K[p];
+    tiles += (grp.N[p] / TN_) * (grp.K[p] / TK_);
+  }
   const int steps = (M + BS - 1) / BS;
   const int unit = 4;  // steps per split: whole 128-row units of the 4-phase kernel
   double best = 1e30;
   int best_sps = (steps + unit - 1) / unit * unit, best_S = 1;
-  for (int S = 1; S <= 128; ++S) {
+  for (int S = 1; S <= 128 && steps > 0; ++S) {
     int sps = (steps + S - 1) / S;
     sps = (sps + unit - 1) / unit * unit;
     if (sps < 4 && S > 1) break;
@@ -584,153 +569,69 @@ int tn_plan(int M, int tiles, long NK, int* S_out) {
   *S_out = best_S;
   return best_sps;
 }
-}  // namespace
-
-int jm_gemm_tn_plan(int M, int N, int K, int* S_out) { return tn_plan(M, (N / TN_) * (K / TK_), (long)N * K, S_out); }
-
-// split plan of a grouped launch: the problems' tiles and output elements together
-int jm_gemm_tn_group_plan(const TnGroup& grp, int M, int* S_out) {
-  long nk = 0;
-  int tiles = 0;
-  for (int p = 0; p < grp.n; ++p) {
-    nk += (long)grp.N[p] * grp.K[p];
-    tiles += (grp.N[p] / TN_) * (grp.K[p] / TK_);
-  }
-  return tn_plan(M, tiles, nk, S_out);
-}
 
 namespace {
-template <typename KERN>
-void set_smem_once(KERN k, bool& done) {
-  if (!done) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jm_gemm_tn_smem());
-    done = true;
-  }
+// launch KERN with the ring's dynamic LDS size, which each instantiation is granted once
+template <auto KERN, typename... Args>
+void tn_launch(int wgs, hipStream_t st, Args... args) {
+  static const hipError_t lds = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                    (int)jm_gemm_tn_smem());
+  (void)lds;
+  KERN<<<wgs, NTH, jm_gemm_tn_smem(), st>>>(args...);
 }
 
-// the 4-phase kernel (whole 128-row units, 64-row segments) or the r1 32-row-step kernel
-// returns 0 (the caller reduces the S partial slices into G when S > 1), < 0 on error
-// store (S == 1): G = the product (the split-0 store kernel into G instead of the accumulating one)
-template <bool SEG>
-int launch_tn(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int sps, int S,
-              float* G, long ldo, float* partial, const TnSegs& segs, bool p4, hipStream_t st, bool store = false) {
-  const int tiles = (N / TN_) * (K / TK_);
-  const size_t sm = jm_gemm_tn_smem();
-  if (S > 1 && partial == nullptr) return -3;
-  if (S == 1 && store) {
-    if (p4) {
-      static bool a = false;
-      set_smem_once(gemm_tn4_kernel<0, SEG>, a);
-      gemm_tn4_kernel<0, SEG><<<tiles, NTH, sm, st>>>(A, lda, B, ldb, M, N, K, sps, G, ldo, 0, segs);
-    } else {
-      static bool a = false;
-      set_smem_once(gemm_tn_kernel<0, SEG>, a);
-      gemm_tn_kernel<0, SEG><<<tiles, NTH, sm, st>>>(A, lda, B, ldb, M, N, K, sps, G, ldo, 0, segs);
-    }
-    return 0;
+// one problem: the 4-phase kernel, or the 32-row-step kernel for blocks that are no multiple of its
+// 64 rows; several: the grouped 4-phase kernel, whose workgroups take every per-problem argument from grp
+template <int ACC>
+void tn_dispatch(const TnGroup& grp, const TnSegs* segs, int M, int sps, int S, hipStream_t st) {
+  const int wgs = grp.tile0[grp.n] * S;
+  const TnSegs sg = segs ? *segs : TnSegs{};
+  if (grp.n > 1) {
+    if (segs)
+      tn_launch<gemm_tn4_kernel<ACC, true, true>>(wgs, st, nullptr, 0, nullptr, 0, M, 0, 0, sps, nullptr, 0, 0, sg, grp);
+    else
+      tn_launch<gemm_tn4_kernel<ACC, false, true>>(wgs, st, nullptr, 0, nullptr, 0, M, 0, 0, sps, nullptr, 0, 0, sg, grp);
+    return;
   }
-  if (p4) {
-    if (S == 1) {
-      static bool a = false;
-      set_smem_once(gemm_tn4_kernel<1, SEG>, a);
-      gemm_tn4_kernel<1, SEG><<<tiles, NTH, sm, st>>>(A, lda, B, ldb, M, N, K, sps, G, ldo, 0, segs);
-    } else {
-      static bool a = false;
-      set_smem_once(gemm_tn4_kernel<0, SEG>, a);
-      gemm_tn4_kernel<0, SEG><<<tiles * S, NTH, sm, st>>>(A, lda, B, ldb, M, N, K, sps, partial, K, (long)N * K,
-                                                          segs);
-    }
-  } else if (S == 1) {
-    static bool a = false;
-    set_smem_once(gemm_tn_kernel<1, SEG>, a);
-    gemm_tn_kernel<1, SEG><<<tiles, NTH, sm, st>>>(A, lda, B, ldb, M, N, K, sps, G, ldo, 0, segs);
-  } else {
-    static bool a = false;
-    set_smem_once(gemm_tn_kernel<0, SEG>, a);
-    gemm_tn_kernel<0, SEG><<<tiles * S, NTH, sm, st>>>(A, lda, B, ldb, M, N, K, sps, partial, K, (long)N * K, segs);
-  }
-  return 0;
+  const int N = grp.N[0], K = grp.K[0];
+  const long ldo = K, ss = S > 1 ? (long)N * K : 0;
+  if (!segs)
+    tn_launch<gemm_tn4_kernel<ACC, false, false>>(wgs, st, grp.a[0], grp.lda[0], grp.b[0], grp.ldb[0], M, N, K, sps,
+                                                  grp.out[0], ldo, ss, sg, TnGroup{});
+  else if (segs->rows % 64 == 0)
+    tn_launch<gemm_tn4_kernel<ACC, true, false>>(wgs, st, grp.a[0], grp.lda[0], grp.b[0], grp.ldb[0], M, N, K, sps,
+                                                 grp.out[0], ldo, ss, sg, TnGroup{});
+  else
+    tn_launch<gemm_tn_kernel<ACC>>(wgs, st, grp.a[0], grp.lda[0], grp.b[0], grp.ldb[0], M, N, K, sps, grp.out[0], ldo,
+                                   ss, sg);
 }
 }  // namespace
 
-
-
-// G[N][K] (ldo) += A[M][N]^T . B[M][K]; partial: [S][N][K] fp32 workspace when S > 1 (else null);
-// the caller reduces the S slices into G (jm_splitk_reduce_add).  Measured and removed: float-atomic
-// split reduction (profiles/r2_tn_atomic.txt), split 0 into G (r1_ab_tn_acc0.txt), the last-arriving
-// split adding the other slices in the kernel (r3e_summary_vitl_b512_fused_reductions.txt).
-int jm_gemm_tn(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int sps, int S,
-               float* G, long ldo, float* partial, hipStream_t st, int store) {
-  if (N % TN_ || K % TK_ || M <= 0) return -1;
-  if ((long)M * lda * 2 >= (1L << 32) || (long)M * ldb * 2 >= (1L << 32)) return -2;
-  return launch_tn<false>(A, lda, B, ldb, M, N, K, sps, S, G, ldo, partial, TnSegs{}, sps % 4 == 0, st, store);
-}
-
-// Segmented-M variant of jm_gemm_tn: A / B rows come from segs (n blocks of segs.rows rows).
-int jm_gemm_tn_seg(const TnSegs& segs, long lda, long ldb, int N, int K, int sps, int S, float* G, long ldo,
-                   float* partial, hipStream_t st, int store) {
-  if (N % TN_ || K % TK_ || segs.n < 1 || segs.n > 32 || segs.rows % BS) return -1;
-  if ((long)segs.rows * lda * 2 >= (1L << 32) || (long)segs.rows * ldb * 2 >= (1L << 32)) return -2;
-  const int M = segs.rows * segs.n;
-  return launch_tn<true>(nullptr, lda, nullptr, ldb, M, N, K, sps, S, G, ldo, partial, segs,
-                         sps % 4 == 0 && segs.rows % 64 == 0, st, store);
-}
-
-// Grouped launch of up to 4 TN problems over the same M rows (e.g. the FF1 and FF2 weight
-// gradients of a layer): one grid of sum(tiles) x S workgroups instead of two half-filled ones,
-// so each problem needs half the splits -- half the fp32 partial slices written and reduced.
-// S > 1: grp.out[p] = the [S][N_p K_p] partial workspace (the caller reduces into G_p); S == 1:
-// grp.out[p] = G_p, accumulated in place.
-int jm_gemm_tn_group(TnGroup grp, int M, int sps, int S, hipStream_t st, int store) {
-  if (grp.n < 1 || grp.n > 4 || M <= 0 || sps % 4 || sps < 4 || S < 1) return -1;
-  grp.tile0[0] = 0;
-  for (int p = 0; p < grp.n; ++p) {
-    if (grp.N[p] % TN_ || grp.K[p] % TK_ || grp.out[p] == nullptr) return -1;
-    if ((long)M * grp.lda[p] * 2 >= (1L << 32) || (long)M * grp.ldb[p] * 2 >= (1L << 32)) return -2;
-    grp.tile0[p + 1] = grp.tile0[p] + (grp.N[p] / TN_) * (grp.K[p] / TK_);
-  }
-  const size_t sm = jm_gemm_tn_smem();
-  const int wgs = grp.tile0[grp.n] * S;
-  if (S == 1 && !store) {
-    static bool a = false;
-    set_smem_once(gemm_tn4_kernel<1, false, true>, a);
-    gemm_tn4_kernel<1, false, true><<<wgs, NTH, sm, st>>>(nullptr, 0, nullptr, 0, M, 0, 0, sps, nullptr, 0, 0,
-                                                          TnSegs{}, grp);
-  } else {
-    static bool a = false;
-    set_smem_once(gemm_tn4_kernel<0, false, true>, a);
-    gemm_tn4_kernel<0, false, true><<<wgs, NTH, sm, st>>>(nullptr, 0, nullptr, 0, M, 0, 0, sps, nullptr, 0, 0,
-                                                          TnSegs{}, grp);
-  }
-  return 0;
-}
-
-// Grouped + segmented (the batched jumbo-MLP weight gradients W1 and W2 of all layers in one
-// grid): problem p's per-layer blocks at segs.a / segs.b[32 p + i], one M split (S == 1, the
-// gradients accumulated in place) when the problems' tiles fill the chip, else partial slices.
-int jm_gemm_tn_group_seg(TnGroup grp, const TnSegs& segs, int sps, int S, hipStream_t st, int store) {
-  const int M = segs.rows * segs.n;
-  if (grp.n < 1 || grp.n > 2 || segs.n < 1 || segs.n > 32 || segs.rows % 64 || sps % 4 || sps < 4 || S < 1)
+// The weight-gradient launch (jm_api.h): G_p[N_p][K_p] (+)= A_p[M][N_p]^T . B_p[M][K_p] for grp's
+// problems in one grid of sum(tiles) x S workgroups -- grouped problems (e.g. the FF1 and FF2
+// gradients of a layer) fill the chip with half the splits of separate launches, i.e. half the fp32
+// partial slices written and reduced.  The caller reduces the S slices into G_p when S > 1
+// (jm_splitk_reduce_add).  Measured and removed: float-atomic split reduction
+// (profiles/r2_tn_atomic.txt), split 0 into G (r1_ab_tn_acc0.txt), the last-arriving split adding
+// the other slices in the kernel (r3e_summary_vitl_b512_fused_reductions.txt).
+int jm_gemm_tn(const TnGroup& g, const TnSegs* segs, int M, int sps, int S, hipStream_t st, int store) {
+  TnGroup grp = g;
+  if (grp.n < 1 || grp.n > (segs ? 2 : 4) || M <= 0 || sps % 4 || sps < 4 || S < 1) return -1;
+  // the S splits cover the M rows and none is empty (the kernels rely on both)
+  const long split_rows = (long)sps * BS;
+  if (S * split_rows < M || (S - 1) * split_rows >= M) return -1;
+  if (segs && (segs->n < 1 || segs->n > 32 || segs->rows % (grp.n > 1 ? 64 : BS) || (long)segs->rows * segs->n != M))
     return -1;
+  const long span = segs ? segs->rows : M;  // rows behind one buffer descriptor
   grp.tile0[0] = 0;
   for (int p = 0; p < grp.n; ++p) {
-    if (grp.N[p] % TN_ || grp.K[p] % TK_ || grp.out[p] == nullptr) return -1;
-    if ((long)segs.rows * grp.lda[p] * 2 >= (1L << 32) || (long)segs.rows * grp.ldb[p] * 2 >= (1L << 32)) return -2;
+    if (grp.N[p] <= 0 || grp.K[p] <= 0 || grp.N[p] % TN_ || grp.K[p] % TK_) return -1;
+    if (span * grp.lda[p] * 2 >= (1L << 32) || span * grp.ldb[p] * 2 >= (1L << 32)) return -2;
+    if (grp.out[p] == nullptr) return -3;
     grp.tile0[p + 1] = grp.tile0[p] + (grp.N[p] / TN_) * (grp.K[p] / TK_);
   }
-  const size_t sm = jm_gemm_tn_smem();
-  const int wgs = grp.tile0[grp.n] * S;
-  if (S == 1 && !store) {
-    static bool a = false;
-    set_smem_once(gemm_tn4_kernel<1, true, true>, a);
-    gemm_tn4_kernel<1, true, true><<<wgs, NTH, sm, st>>>(nullptr, 0, nullptr, 0, M, 0, 0, sps, nullptr, 0, 0, segs,
-                                                         grp);
-  } else {
-    static bool a = false;
-    set_smem_once(gemm_tn4_kernel<0, true, true>, a);
-    gemm_tn4_kernel<0, true, true><<<wgs, NTH, sm, st>>>(nullptr, 0, nullptr, 0, M, 0, 0, sps, nullptr, 0, 0, segs,
-                                                         grp);
-  }
+  if (S == 1 && !store) tn_dispatch<1>(grp, segs, M, sps, S, st);
+  else tn_dispatch<0>(grp, segs, M, sps, S, st);
   return 0;
 }
 

@@ -1,6 +1,13 @@
-// Host-side argument structs shared by the kernel translation units and bindings.cpp.
+// The host interface of the kernel translation units: every jm_* entry point that bindings.cpp (or
+// another translation unit) calls, and the argument structs that cross that boundary.  This header
+// is the only place where they are declared -- default arguments included -- and every *.hip file
+// and bindings.cpp include it (hipcc and g++), so a definition that drifts from its declaration
+// fails to link and a struct has one layout everywhere.
 #pragma once
+#include <cstddef>
 #include <cstdint>
+
+#include <hip/hip_runtime.h>
 
 // Dense-output dropout applied by the residual kernels that consume the branch output y (ops/blocks.py
 // Drops): the element at y + o (y's own element offset o) is kept with common.h drop_keep(seed, ioff + o),
@@ -27,10 +34,10 @@ struct JmLnRes {
   JmDrop drop;  // y's dropout (dy and dscale use the masked y)
 };
 
-// Grouped weight-gradient launch (gemm_tn.hip jm_gemm_tn_group): n <= 4 independent TN problems
+// A weight-gradient launch (gemm_tn.hip jm_gemm_tn): n <= 4 independent TN problems
 // G_p[N_p][K_p] (+)= A_p[M][N_p]^T . B_p[M][K_p] over the SAME M rows in one grid; tile0 = prefix
-// sums of the problems' 256 x 256 output tiles; out[p] = G_p (one split) or its [S][N_p K_p]
-// fp32 partial slices.
+// sums of the problems' 256 x 256 output tiles (filled by jm_gemm_tn); out[p] = G_p (one split)
+// or its [S][N_p K_p] fp32 partial slices.  With segmented rows a / b stay null (see TnSegs).
 struct TnGroup {
   const uint16_t* a[4];
   const uint16_t* b[4];
@@ -38,6 +45,17 @@ struct TnGroup {
   int N[4], K[4];
   float* out[4];
   int tile0[5];
+  int n;
+};
+
+// Segmented M (the batched shared-jumbo-MLP weight gradient): the reduction rows are the
+// concatenation of ``n`` separately allocated [rows, lda] / [rows, ldb] blocks (one per layer),
+// read in place instead of being copied into one tensor first.  Problem p of a launch keeps its
+// blocks at entries 32 p + i (so a segmented launch has at most 2 problems).
+struct TnSegs {
+  const uint16_t* a[64];
+  const uint16_t* b[64];
+  int rows;  // rows per block, multiple of the 32-row step
   int n;
 };
 
@@ -69,3 +87,201 @@ struct GemmEpi {
   const uint8_t* dqa;
   float dqs;
 };
+
+// ------------------------------------------------------------------------------ entry points
+// int results: 0 (or a count, where the comment says so), < 0 for an unsupported shape or argument.
+// jm_debug_line_<tu> (common.h JM_DEBUG_EXPORT, one per translation unit): the first failing soft
+// device check's source line in the debug build (0 = none; reading clears it), always 0 in release.
+
+// ---- layernorm.hip
+// y (fp32 or bf16 [B T, D]), mean, rstd of the rows of a strided [B, T, D] x; y2: optional bf16 copy of y
+int jm_layernorm_fwd(const float* x, long sB, long sT, int B, int T, int D, const float* gamma, const float* beta,
+                     float eps, void* y, int out_bf16, float* mean, float* rstd, hipStream_t st, uint16_t* y2 = nullptr);
+// dx (+ dres), dgamma, dbeta; res: the fused residual backward (JmLnRes); hx + beta: x rebuilt from the bf16 output
+int jm_layernorm_bwd(const void* dy, int dy_bf16, const float* x, long sB, long sT, int B, int T, int D,
+                     const float* mean, const float* rstd, const float* gamma, float* dx_ptr, long oB, long oT,
+                     const float* dres, long rB, long rT, float* dgamma, float* dbeta, int accum_params, float* ws,
+                     const JmLnRes* res, hipStream_t st, const uint16_t* hx = nullptr,
+                     const float* beta = nullptr);
+// workgroups of jm_layernorm_bwd (= rows of its partial workspace ws)
+int jm_layernorm_bwd_blocks(int rows, int D);
+// x1 = x + mask scale drop(y) on rows t >= R0, and h / mean / rstd = LayerNorm of x1's rows t >= T0
+int jm_residual_ln_fwd(const float* x, long sB, long sT, const uint16_t* y, const float* scale, const float* mask,
+                       float* x1, long oB, long oT, uint16_t* h, float* mean, float* rstd, int B, int T, int T0,
+                       int D, const float* gamma, const float* beta, float eps, hipStream_t st, int R0 = 0,
+                       JmDrop drop = JmDrop{nullptr, 0u, 1.f, 0});
+int jm_debug_line_layernorm();
+
+// ---- elementwise.hip
+// a = gelu(h), bf16, n % 8 == 0
+int jm_gelu_fwd(const uint16_t* h, uint16_t* a, long n, hipStream_t st);
+// floats of the ws argument of the row-column kernels below (nacc column accumulators)
+long jm_rowcol_ws_floats(int M, int N, int nacc);
+// dh = da gelu'(h) (deriv: h already holds gelu'), bias_grad += colsum(dh)
+int jm_gelu_bwd(const uint16_t* h, const uint16_t* da, uint16_t* dh, float* bias_grad, int M, int N, hipStream_t st,
+                int deriv, float* ws);
+// acc += colsum(x), x bf16 [M, N]
+int jm_colsum_bf16(const uint16_t* x, float* acc, int M, int N, hipStream_t st, float* ws);
+// out = x + mask scale drop(y)
+int jm_residual_fwd(const float* x, long sB, long sT, int B, int T, int D, const uint16_t* y, const float* scale,
+                    const float* mask, float* out, long oB, long oT, hipStream_t st, JmDrop drop);
+// dy = bf16(mask scale dout) under y's dropout, dscale += colsum(mask dout y), dbias += colsum(dy)
+int jm_residual_bwd(const float* dout, long dB, long dT, const uint16_t* y, const float* scale, const float* mask,
+                    float* dscale, uint16_t* dy, int B, int T, int D, float* dbias, long yB, long yT, hipStream_t st,
+                    JmDrop drop, float* ws);
+// p[0, n) = 0
+void jm_zero_f32(float* p, long n, hipStream_t st);
+// g (+)= the sum of the S fp32 slices part[s][n]; store: g's old contents are ignored
+int jm_splitk_reduce_add(const float* part, float* g, long n, int S, hipStream_t st, int store = 0);
+// g += the column sums of the row-strided fp32 [rows, n] view x
+int jm_colsum_add_f32(const float* x, long ld, int rows, long n, float* g, hipStream_t st);
+// zero the n (offset, count) float ranges of base listed in the device array desc
+int jm_zero_ranges(float* base, const long long* desc, int n, long long blocks, hipStream_t st);
+// dst [C, R] = src [R, C]^T, bf16
+int jm_transpose_bf16(const uint16_t* src, uint16_t* dst, int R, int C, hipStream_t st);
+// the n transposes {src, dst, R, C, first tile, tiles along C} of the device array desc in one launch
+int jm_transpose_bf16_batch(const long long* desc, int n, int tiles, hipStream_t st);
+// out (bf16 [n / N, N]) = the sum of the S split-K slices + bias
+int jm_splitk_reduce_bf16(const float* part, int S, long n, int N, const float* bias, uint16_t* out, hipStream_t st);
+// out (fp32 [M, N]) = the sum of the S split-K slices + bias + add
+int jm_splitk_reduce_f32(const float* part, int S, int M, int N, const float* bias, const float* add, long add_ld,
+                         float* out, hipStream_t st);
+int jm_debug_line_elementwise();
+// debug build: one wave fails a soft check iff v != 0 (the test of the debug_lines() plumbing)
+void jm_debug_selftest(int v, hipStream_t st);
+
+// ---- attention.hip
+// o, lse = softmax(q k^T / sqrt(hd)) v per head of the packed bf16 qkv [B, S, 3 H hd]; dseed: probability dropout
+int jm_attn_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int S, int H, int hd, const int64_t* dseed,
+                uint32_t dthr, float dscale, hipStream_t st);
+// whole-sequence backward (-2 where jm_attn_tiled); dbias_part: optional per-sample column sums of dqkv
+int jm_attn_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv, int B,
+                int S, int H, int hd, float* dbias_part, const int64_t* dseed, uint32_t dthr, float dscale,
+                hipStream_t st);
+// tile-streamed backward (jm_attn_tiled shapes); delta: fp32 [B][H][S] workspace
+int jm_attn_bwd_long(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse, uint16_t* dqkv,
+                     float* delta, int B, int S, int H, int hd, const int64_t* dseed, uint32_t dthr, float dscale,
+                     hipStream_t st);
+// longest sequence of the whole-sequence kernels
+int jm_attn_max_seq();
+// the head dims that have kernels (returns their count)
+int jm_attn_head_dims(const int** dims);
+// 1: (S, hd) runs on the tile-streamed kernels
+int jm_attn_tiled(int S, int hd);
+// 1: jm_attn_bwd can add the QKV bias gradient (dbias_part)
+int jm_attn_fused_bias(int S, int hd);
+// rows of jm_attn_bwd's dbias_part workspace
+int jm_attn_bwd_part_rows(int B, int S, int hd);
+// 1: the kernels of (S, hd) take a dropout seed
+int jm_attn_dropout(int S, int hd);
+int jm_debug_line_attention();
+
+// ---- optim.hip (chunks: the device chunk table of the flat parameter buffer)
+// out = the sum of squares of x
+void jm_opt_sumsq(const float* x, const int* chunks, int nchunks, float* out, float* cpart, hipStream_t st);
+// one AdamW step on the flat buffers (+ the bf16 shadow copy of p)
+void jm_opt_adamw(float* p, const float* g, float* mu, float* nu, uint16_t* shadow, const int* chunks, int nchunks,
+                  const float* meta, const float* hyper, const float* gnorm_sq, hipStream_t st);
+// LAMB: moments, the update u and the per-tensor norms of p and u
+void jm_opt_lamb_phase1(const float* p, const float* g, float* mu, float* nu, float* u, const int* chunks, int nchunks,
+                        const float* meta, const float* hyper, const float* gnorm_sq, float* norms, float* cpart,
+                        hipStream_t st);
+// LARS: the per-tensor norms of p and g
+void jm_opt_lars_norms(const float* p, const float* g, const int* chunks, int nchunks, const float* hyper,
+                       const float* gnorm_sq, float* norms, float* cpart, hipStream_t st);
+// LAMB / LARS: apply the update scaled by the per-tensor trust ratio
+void jm_opt_apply_trust(float* p, const float* u_or_g, float* trace, uint16_t* shadow, const int* chunks, int nchunks,
+                        const float* meta, const float* hyper, const float* norms, const float* gnorm_sq, int mode,
+                        float momentum, float trust_coef, hipStream_t st);
+// one SGD (momentum) step
+void jm_opt_sgd(float* p, const float* g, float* trace, uint16_t* shadow, const int* chunks, int nchunks,
+                const float* meta, const float* hyper, const float* gnorm_sq, float momentum, hipStream_t st);
+int jm_debug_line_optim();
+
+// ---- mae.hip
+// out = the normalized p x p patches of the uint8 images, fp32
+int jm_patchify_normalize(const uint8_t* img, float* out, int B, int H, int W, int p, hipStream_t st);
+// out = the normalized patches ids[b, k] of each image, bf16
+int jm_gather_patches(const uint8_t* img, const int* ids, long idsB, uint16_t* out, int B, int K, int H, int W, int p,
+                      hipStream_t st);
+// out = [class tokens; patch embeddings e + their position embeddings], fp32
+int jm_embed_finish(const uint16_t* e, const float* pos, const int* ids, long idsB, const float* cls, float* out,
+                    int B, int C, int K, int D, hipStream_t st);
+// random-masking ids and mask from noise [R, N]: stable argsort, its inverse, their int32 copies
+int jm_mask_ids(const float* noise, int R, int N, int keep, int64_t* shuffle, int64_t* restore, int* keep32,
+                int* restore32, float* mask, hipStream_t st);
+// decoder input: kept tokens / mask tokens back in image order + position embeddings
+int jm_unshuffle_fwd(const uint16_t* y, const float* tok, const int* restore, long rsB, const float* pos, float* out,
+                     int B, int C, int K, int N, int d, hipStream_t st);
+// partial rows that jm_unshuffle_bwd writes to part
+int jm_unshuffle_bwd_blocks(int B, int C, int N, int rows_per_block);
+// its backward: dy for the kept tokens, per-block partial sums of the mask-token gradient
+int jm_unshuffle_bwd(const float* dout, const int* restore, long rsB, uint16_t* dy, float* part, int B, int C, int K,
+                     int N, int d, int rows_per_block, hipStream_t st);
+// the patches of the mixup / cutmix of each image with image perm[b], bf16
+int jm_mix_patches(const uint8_t* img, const int* perm, const float* prm, const int* box, uint16_t* out, int B, int H,
+                   int W, int p, hipStream_t st);
+// per-patch MSE of pred against the (norm_pix: per-patch normalized) image patches
+int jm_patch_mse_fwd(const uint16_t* pred, long ldp, const uint8_t* img, float* mse, long rows, int N, int H, int W,
+                     int p, int norm_pix, hipStream_t st);
+int jm_patch_mse_bwd(const uint16_t* pred, long ldp, const uint8_t* img, const float* dmse, uint16_t* dpred, long rows,
+                     int N, int H, int W, int p, int norm_pix, hipStream_t st);
+int jm_debug_line_mae();
+
+// ---- gemm.hip
+// C = A[M, K] . B[N, K]^T on the MFMA kernels with epilogue epi (GemmEpi)
+int jm_gemm_nt(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int epi,
+               const GemmEpi& ep, hipStream_t st);
+// output tiles (workgroups before split-K) of that launch
+int jm_gemm_nt_tiles(int M, int N, int K, int epi, long lda);
+// rows of its colpart output (EPI_DGELU)
+int jm_gemm_nt_colpart_rows(int M, int N, int K, int epi, long lda);
+// tail split of that launch: returns tail_S, *tail_r tiles, *ws_floats of workspace (0: none)
+int jm_gemm_nt_tail_plan(int M, int N, int K, int epi, long lda, int* tail_r, long* ws_floats);
+// numerics tests only: force a kernel path (0 = by shape)
+void jm_gemm_test_force(int path, int rows);
+int jm_debug_line_gemm();
+
+// ---- gemm_tn.hip
+// dynamic LDS bytes of the weight-gradient kernels
+size_t jm_gemm_tn_smem();
+// M split of a launch over grp's problems (N, K, n read): returns the 32-row steps per split (a
+// multiple of 4), *S_out = the number of splits
+int jm_gemm_tn_plan(const TnGroup& grp, int M, int* S_out);
+// the launch: contiguous rows a / b (segs null) or the blocks of segs (M = segs->rows segs->n);
+// S > 1: out[p] = the [S][N_p K_p] partial slices (the caller reduces them), S == 1: out[p] = G_p,
+// accumulated, or stored with store != 0.  -1 shape, -2 operand rows of 4 GiB or more, -3 null output
+int jm_gemm_tn(const TnGroup& grp, const TnSegs* segs, int M, int sps, int S, hipStream_t st, int store);
+int jm_debug_line_gemm_tn();
+
+// ---- dropout.hip (seed: int64 [1] on the device, thr = round(keep 65536), scale = 1 / keep)
+// y = dropout(x), n % 8 == 0, bf16 or fp32
+int jm_dropout_apply(const void* x, void* y, long n, int bf16, const int64_t* seed, uint32_t thr, float scale,
+                     hipStream_t st);
+// h null: g, gp masked in place; else g = gelu(h) m, gp = gelu'(h) m
+int jm_gelu_drop(const uint16_t* h, uint16_t* g, uint16_t* gp, long n, const int64_t* seed, uint32_t thr, float scale,
+                 hipStream_t st);
+// p = softmax(z) over rows of S, pd = dropout(p)
+int jm_softmax_dropout_fwd(const float* z, float* p, float* pd, long rows, int S, const int64_t* seed, uint32_t thr,
+                           float scale, hipStream_t st);
+int jm_softmax_dropout_bwd(const float* dpd, const float* p, float* dz, long rows, int S, const int64_t* seed,
+                           uint32_t thr, float scale, hipStream_t st);
+int jm_debug_line_dropout();
+
+// ---- augment.hip
+// random-resized-crop: the crop windows of src (table tab) resized to out [B, 3, S, S] uint8
+int jm_rrc_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t* tmp, int tmp_rows_max, uint8_t* out,
+                  hipStream_t st);
+// the most filter taps per output pixel that the resize kernels take
+int jm_rrc_kmax();
+int jm_debug_line_augment();
+
+// ---- augment_chain.hip
+// uint32 words per image of jm_aug_chain's stats
+int jm_aug_stat_words();
+// doubles per slot of its chain records
+int jm_aug_record_len();
+// the RandAugment op chain of every image on the ping-pong buffers; returns the buffer with the result (0 / 1)
+int jm_aug_chain(uint8_t* images, uint8_t* scratch, const double* chain, int B, int slots, int S, uint32_t* stats,
+                 hipStream_t st);
+int jm_debug_line_augment_chain();

@@ -5,6 +5,7 @@
 // ((x/255) - mean) / std (pretraining.py:90-91).  One workgroup per (image, patch row): the
 // 3 x p x W uint8 strip is staged through LDS with 4-byte loads, then written out coalesced.
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 

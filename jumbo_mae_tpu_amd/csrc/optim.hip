@@ -8,6 +8,7 @@
 // and the optional global grad norm^2 (negative = clipping off), so the step is graph-capturable.
 // Semantics: optax adamw / modified LAMB / lars / sgd (see optim/flat.py for the reference map).
 #include "common.h"
+#include "jm_api.h"
 
 namespace {
 

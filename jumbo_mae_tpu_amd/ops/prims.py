@@ -53,6 +53,13 @@ def wgrad_split(M: int, N: int, K: int) -> int:
 _WGRAD_OURS = True
 
 
+def _tn_ok(dy: torch.Tensor, x: torch.Tensor) -> bool:
+    """``wgrad`` runs this (dy, x) on the TN MFMA kernel (csrc/gemm_tn.hip)."""
+    return (_WGRAD_OURS and hip(dy) and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dy.dim() == 2
+            and dy.shape[1] % 256 == 0 and x.shape[1] % 256 == 0 and dy.shape[0] >= 4096
+            and dy.stride(1) == 1 and x.stride(1) == 1)
+
+
 def wgrad(h: Handle, dy: torch.Tensor, x: torch.Tensor, rows: tuple[int, int] | None = None) -> None:
     """grad[h] += dy^T @ x  (fp32 accumulate; bf16 inputs on GPU); ``rows`` = (r0, r1) restricts
     it to gradient rows r0:r1 (``dy`` then holds only those output columns).
@@ -64,8 +71,7 @@ def wgrad(h: Handle, dy: torch.Tensor, x: torch.Tensor, rows: tuple[int, int] | 
     if dy.is_cuda and dy.dtype != torch.float32:
         M, N = dy.shape
         K = x.shape[1]
-        if (_WGRAD_OURS and hip(dy) and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-                and N % 256 == 0 and K % 256 == 0 and M >= 4096 and dy.stride(1) == 1 and x.stride(1) == 1):
+        if _tn_ok(dy, x):
             # whole-gradient writes may store (ParamStore.zero_grad skipped it); row slices settle
             store = h.take_store() if rows is None else False
             if rows is not None:
@@ -90,13 +96,6 @@ def wgrad(h: Handle, dy: torch.Tensor, x: torch.Tensor, rows: tuple[int, int] | 
             torch.addmm(g, dy.t(), x, out_dtype=torch.float32, out=g)
     else:
         g.addmm_(dy.t().float(), x.float())
-
-
-def _tn_ok(dy: torch.Tensor, x: torch.Tensor) -> bool:
-    """``wgrad`` runs this (dy, x) on the TN MFMA kernel (csrc/gemm_tn.hip)."""
-    return (_WGRAD_OURS and hip(dy) and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dy.dim() == 2
-            and dy.shape[1] % 256 == 0 and x.shape[1] % 256 == 0 and dy.shape[0] >= 4096
-            and dy.stride(1) == 1 and x.stride(1) == 1)
 
 
 # ------------------------------------------------------------- paired weight gradients

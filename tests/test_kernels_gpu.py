@@ -466,6 +466,72 @@ def test_gemm_tn_wgrad_seg_group(ext, nb, rows):
         assert rel(g, r) < 1e-4
 
 
+def test_gemm_tn_wgrad_forms_agree(ext):
+    """The four entry points are adaptors of one host path: a grouped call with a single problem
+    runs the same kernel as the plain call -- every output element has one writer and the split
+    reduction has a fixed order, so the results are bit-equal.  (a) contiguous rows; (b) row
+    blocks of 64 rows (the 4-phase kernel) and of 96 rows (the 32-row-step kernel), also against
+    the fp64 product."""
+    torch.manual_seed(0)
+    N = K = 256
+    dy = (torch.rand(4096, N, device="cuda") * 2 - 1).bfloat16()
+    x = (torch.rand(4096, K, device="cuda") * 2 - 1).bfloat16()
+    g0 = torch.randn(N, K, device="cuda")
+    g1, g2 = g0.clone(), g0.clone()
+    assert ext.gemm_tn_wgrad(dy, x, g1) == ext.gemm_tn_wgrad_group([dy], [x], [g2])
+    assert torch.equal(g1, g2) and not torch.equal(g1, g0)
+    for rows in (64, 96):
+        dys = [(torch.rand(rows, N, device="cuda") * 2 - 1).bfloat16() for _ in range(3)]
+        xs = [(torch.rand(rows, K, device="cuda") * 2 - 1).bfloat16() for _ in range(3)]
+        ref = g0.double() + torch.cat(dys).double().t() @ torch.cat(xs).double()
+        g1, g2 = g0.clone(), g0.clone()
+        assert ext.gemm_tn_wgrad_seg(dys, xs, g1) == ext.gemm_tn_wgrad_seg_group([dys], [xs], [g2])
+        assert torch.equal(g1, g2), rows
+        assert rel(g1, ref) < 1e-4, rows
+
+
+def _tn_call(ext, form, dys, xs, gs):
+    """The same problems (one row block each) through one of the four weight-gradient entry points;
+    the single-problem forms take the first."""
+    if form == "wgrad":
+        return ext.gemm_tn_wgrad(dys[0], xs[0], gs[0])
+    if form == "seg":
+        return ext.gemm_tn_wgrad_seg([dys[0]], [xs[0]], gs[0])
+    if form == "group":
+        return ext.gemm_tn_wgrad_group(dys, xs, gs)
+    return ext.gemm_tn_wgrad_seg_group([[d] for d in dys], [[x] for x in xs], gs)
+
+
+@pytest.mark.parametrize("bad", ["cpu_g", "cpu_operand", "different_M", "N_192", "fp16_operand"])
+@pytest.mark.parametrize("form", ["wgrad", "seg", "group", "seg_group"])
+def test_gemm_tn_wgrad_rejects(ext, form, bad):
+    """Every entry point refuses the same bad arguments with a RuntimeError before anything is
+    launched (the gradients keep their contents); the good arguments of the same shapes run."""
+    torch.manual_seed(0)
+    M, N, K = 128, 256, 256
+    mk = lambda m, n: (torch.rand(m, n, device="cuda") * 2 - 1).bfloat16()
+    dys, xs = [mk(M, N), mk(M, N)], [mk(M, K), mk(M, K)]
+    gs = [torch.randn(N, K, device="cuda") for _ in range(2)]
+    _tn_call(ext, form, dys, xs, gs)
+    if bad == "cpu_g":
+        gs[0] = gs[0].cpu()
+    elif bad == "cpu_operand":
+        xs[0] = xs[0].cpu()
+    elif bad == "different_M" and form in ("wgrad", "seg"):
+        xs[0] = mk(M + 64, K)
+    elif bad == "different_M":
+        dys[1], xs[1] = mk(M + 64, N), mk(M + 64, K)
+    elif bad == "N_192":
+        dys[0], gs[0] = mk(M, 192), torch.randn(192, K, device="cuda")
+    else:
+        dys[0] = dys[0].half()
+    before = [g.clone() for g in gs]
+    with pytest.raises(RuntimeError):
+        _tn_call(ext, form, dys, xs, gs)
+    torch.cuda.synchronize()
+    assert all(torch.equal(g, b) for g, b in zip(gs, before))
+
+
 @pytest.mark.parametrize("T0", [0, 3])
 @pytest.mark.parametrize("with_scale", [False, True])
 def test_residual_ln_fwd(ext, T0, with_scale):
