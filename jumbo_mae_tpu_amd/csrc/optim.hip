@@ -109,7 +109,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     const float u = (mm * ib1) / (sqrtf(vv * ib2) + eps) + wd * pv;
     return pv + step * u;
   };
-  // 16 B per lane (chunk starts are multiples of 64 elements).  Same step time as the r1
+  // 16 B per lane: chunk starts are multiples of 4 elements -- segment offsets and CHUNK are, and
+  // ZeRO-1 piece boundaries are multiples of 64 (tests/test_optim.py
+  // test_chunk_starts_are_16_byte_aligned); offsets are NOT all multiples of 64, the segments of a
+  // fused handle stay adjacent.  A chunk's last len % 4 elements take the scalar loop below.  Same
+  // step time as the r1
   // 4-B-per-lane loop in a same-process A/B (profiles/r2_adamw_vector.txt: the pass is HBM-bound
   // either way; its 2.1-2.4 ms spread is box to box)
   const int n4 = c.len >> 2;
