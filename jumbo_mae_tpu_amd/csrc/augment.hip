@@ -1,4 +1,5 @@
-// Device-side RandomResizedCrop (bicubic) + horizontal flip of decoded uint8 images (gfx950).
+// Device-side RandomResizedCrop (bicubic) + horizontal flip, and the validation transform
+// Resize (bicubic) + CenterCrop, of decoded uint8 images (gfx950).
 //
 // The pretraining input transform (reference src/dataset.py:56-82: RandomResizedCrop(224,
 // scale=(0.2, 1), bicubic) -> RandomHorizontalFlip -> PILToTensor) costs a loader worker ~1.4 ms
@@ -19,6 +20,24 @@
 //
 // Per-image table (int64 x RRC_TAB): src offset, window rows / cols, window origin y0 / x0, image
 // H / W, crop i / j / h / w (PIL box (j, i, j + w, i + h)), flip, offset of its rows in tmp.
+//
+// Window resize (jm_window_resize, the validation transform Resize(R, bicubic) -> CenterCrop(S) ->
+// PILToTensor, data/loader.py DeviceValidParams): the same two kernels, instantiated for a wider
+// table (int64 x WIN_TAB) whose output is an S x S WINDOW of a larger resize.  Columns 0 .. 12 as
+// above (the box is the whole image and flip is 0 on the validation path), then
+//   13 / 14  oh / ow  the full resize's output rows / columns (Resize's nh / nw): each axis is
+//                     make_axis(in_size, box0, box1, oh | ow)
+//   15 / 16  oi / oj  the window's origin in that output (CenterCrop's i0 / j0): output pixel (y, x)
+//                     takes the coefficients of (oi + y, oj + x) of the full resize -- the centre is
+//                     in0 + (oj + x + 0.5) * scale, NOT a shifted in0, which would round differently
+//   17       fill     1: a pad row of a validation batch padded to its static size (collate_and_pad:
+//                     images 255, labels -1); window rows / cols are 0, its blocks write 255 to all
+//                     3 S S bytes and read neither src nor tmp.
+// The coefficients of an output pixel depend on its coordinate, the scale and the input size only,
+// and the 8-bit intermediate is per (row, output column), so the window equals those pixels of
+// Pillow's full resize bit for bit; the horizontal pass writes only the window's S columns of the
+// rows that the vertical pass of its S rows reads.  The 13-column table is the window (0, 0) of an
+// S x S resize.
 #include "common.h"
 #include "jm_api.h"
 
@@ -26,6 +45,7 @@ namespace {
 
 constexpr int PB = 22;  // Pillow PRECISION_BITS = 32 - 8 - 2
 constexpr int RRC_TAB = 13;
+constexpr int WIN_TAB = 18;
 constexpr int RRC_KMAX = 24;  // taps: support 2 x scale -> crops up to 5.75 x the output size
 constexpr int RRC_VROWS = 16;
 
@@ -96,10 +116,12 @@ JM_DEVICE uint8_t clip8(int v) {
 struct Img {
   long src, tmp;
   int wh, ww, y0, x0, H, W, i, j, ch, cw, flip;
+  int oh, ow, oi, oj, fill;  // full output size, the window's origin in it, pad row
 };
 
-JM_DEVICE Img load_img(const int64_t* __restrict__ tab, int b) {
-  const int64_t* t = tab + (long)b * RRC_TAB;
+template <int TAB>
+JM_DEVICE Img load_img(const int64_t* __restrict__ tab, int b, int S) {
+  const int64_t* t = tab + (long)b * TAB;
   Img m;
   m.src = t[0];
   m.wh = (int)t[1];
@@ -114,31 +136,48 @@ JM_DEVICE Img load_img(const int64_t* __restrict__ tab, int b) {
   m.cw = (int)t[10];
   m.flip = (int)t[11];
   m.tmp = t[12];
+  if constexpr (TAB == WIN_TAB) {
+    m.oh = (int)t[13];
+    m.ow = (int)t[14];
+    m.oi = (int)t[15];
+    m.oj = (int)t[16];
+    m.fill = (int)t[17];
+  } else {
+    m.oh = m.ow = S;
+    m.oi = m.oj = 0;
+    m.fill = 0;
+  }
   return m;
 }
 
-// rows [first, last) of the source that the vertical pass reads
+// rows [first, last) of the source that the vertical pass of the window's S output rows reads
 JM_DEVICE void vrows(const Img& m, int S, int& first, int& last) {
-  const Axis av = make_axis(m.H, (float)m.i, (float)(m.i + m.ch), S);
+  const Axis av = make_axis(m.H, (float)m.i, (float)(m.i + m.ch), m.oh);
   double c;
   int y;
-  axis_bounds(av, 0, c, first);
-  const int n = axis_bounds(av, S - 1, c, y);
+  axis_bounds(av, m.oi, c, first);
+  const int n = axis_bounds(av, m.oi + S - 1, c, y);
   last = y + n;
 }
 
+template <int TAB>
 __global__ __launch_bounds__(256) void rrc_h_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ tab,
                                                     uint8_t* __restrict__ tmp, int S, int rows_per_blk) {
-  const Img m = load_img(tab, blockIdx.x);
+  const Img m = load_img<TAB>(tab, blockIdx.x, S);
+  if (m.fill) return;  // pad row: nothing to read
+  JM_DASSERT(m.oi >= 0 && m.oj >= 0 && m.oi + S <= m.oh && m.oj + S <= m.ow);
   int first, last;
   vrows(m, S, first, last);
+  // the shipped window holds every row the vertical pass reads, and tmp has a row for each
+  JM_DASSERT(first >= m.y0 && last <= m.y0 + m.wh);
   const int r0 = first + blockIdx.y * rows_per_blk;
   const int r1 = min(last, r0 + rows_per_blk);
   if (r0 >= r1) return;
-  const Axis ah = make_axis(m.W, (float)m.j, (float)(m.j + m.cw), S);
+  const Axis ah = make_axis(m.W, (float)m.j, (float)(m.j + m.cw), m.ow);
   for (int xx = threadIdx.x; xx < S; xx += blockDim.x) {
     int k[RRC_KMAX], xmin;
-    const int n = axis_taps(ah, xx, k, xmin);
+    const int n = axis_taps(ah, m.oj + xx, k, xmin);
+    JM_DASSERT(n <= RRC_KMAX && xmin >= m.x0 && xmin + n <= m.x0 + m.ww);
     const uint8_t* base = src + m.src + (long)(xmin - m.x0) * 3;
     for (int r = r0; r < r1; ++r) {
       const uint8_t* p = base + (long)(r - m.y0) * m.ww * 3;
@@ -159,27 +198,38 @@ __global__ __launch_bounds__(256) void rrc_h_kernel(const uint8_t* __restrict__ 
   }
 }
 
+template <int TAB>
 __global__ __launch_bounds__(256) void rrc_v_kernel(const uint8_t* __restrict__ tmp, const int64_t* __restrict__ tab,
                                                     uint8_t* __restrict__ out, int S) {
   __shared__ int kv[RRC_VROWS][RRC_KMAX];
   __shared__ int vmin[RRC_VROWS], vn[RRC_VROWS];
   const int b = blockIdx.x;
-  const Img m = load_img(tab, b);
+  const Img m = load_img<TAB>(tab, b, S);
+  const int yy0 = blockIdx.y * RRC_VROWS;
+  const long plane = (long)S * S;
+  uint8_t* ob = out + (long)b * 3 * plane;
+  if (m.fill) {  // pad row (uniform per block, before the barrier): 255 everywhere, no reads
+    const int rows = min(RRC_VROWS, S - yy0);
+    for (int c = 0; c < 3; ++c) {
+      uint8_t* o = ob + c * plane + (long)yy0 * S;
+      for (int e = threadIdx.x; e < rows * S; e += blockDim.x) o[e] = 255;
+    }
+    return;
+  }
   int first, last;
   vrows(m, S, first, last);
-  const int yy0 = blockIdx.y * RRC_VROWS;
   if (threadIdx.x < RRC_VROWS && yy0 + (int)threadIdx.x < S) {
-    const Axis av = make_axis(m.H, (float)m.i, (float)(m.i + m.ch), S);
+    const Axis av = make_axis(m.H, (float)m.i, (float)(m.i + m.ch), m.oh);
     int k[RRC_KMAX], ymin;
-    const int n = axis_taps(av, yy0 + threadIdx.x, k, ymin);
+    const int n = axis_taps(av, m.oi + yy0 + threadIdx.x, k, ymin);
+    // the taps lie in the rows [first, last) that the horizontal pass wrote
+    JM_DASSERT(n <= RRC_KMAX && ymin >= first && ymin + n <= last && last - first <= m.wh);
 #pragma unroll
     for (int x = 0; x < RRC_KMAX; ++x) kv[threadIdx.x][x] = k[x];
     vmin[threadIdx.x] = ymin - first;
     vn[threadIdx.x] = n;
   }
   __syncthreads();
-  const long plane = (long)S * S;
-  uint8_t* ob = out + (long)b * 3 * plane;
   for (int r = 0; r < RRC_VROWS && yy0 + r < S; ++r) {
     const int yy = yy0 + r, n = vn[r];
     const uint8_t* base = tmp + m.tmp + (long)vmin[r] * S * 3;
@@ -210,11 +260,27 @@ int jm_rrc_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t*
                   uint8_t* out, hipStream_t st) {
   if (B <= 0 || S <= 0 || S > 4096 || tmp_rows_max <= 0) return -1;
   const int rows_per_blk = 32;
-  rrc_h_kernel<<<dim3(B, (tmp_rows_max + rows_per_blk - 1) / rows_per_blk), 256, 0, st>>>(src, tab, tmp, S,
-                                                                                         rows_per_blk);
-  rrc_v_kernel<<<dim3(B, (S + RRC_VROWS - 1) / RRC_VROWS), 256, 0, st>>>(tmp, tab, out, S);
+  rrc_h_kernel<RRC_TAB><<<dim3(B, (tmp_rows_max + rows_per_blk - 1) / rows_per_blk), 256, 0, st>>>(src, tab, tmp, S,
+                                                                                                  rows_per_blk);
+  rrc_v_kernel<RRC_TAB><<<dim3(B, (S + RRC_VROWS - 1) / RRC_VROWS), 256, 0, st>>>(tmp, tab, out, S);
   return 0;
 }
+
+// The same for the [B, WIN_TAB] table (see top): out[b] = the S x S window (oi, oj) of image b's
+// resize to oh x ow, or all 255 for a pad row.  tmp_rows_max may be 0 (a batch of pad rows only:
+// the horizontal pass is not launched and src / tmp are not read).
+int jm_window_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t* tmp, int tmp_rows_max,
+                     uint8_t* out, hipStream_t st) {
+  if (B <= 0 || S <= 0 || S > 4096 || tmp_rows_max < 0) return -1;
+  const int rows_per_blk = 32;
+  if (tmp_rows_max > 0)
+    rrc_h_kernel<WIN_TAB><<<dim3(B, (tmp_rows_max + rows_per_blk - 1) / rows_per_blk), 256, 0, st>>>(src, tab, tmp, S,
+                                                                                                    rows_per_blk);
+  rrc_v_kernel<WIN_TAB><<<dim3(B, (S + RRC_VROWS - 1) / RRC_VROWS), 256, 0, st>>>(tmp, tab, out, S);
+  return 0;
+}
+
+int jm_window_tab() { return WIN_TAB; }
 
 int jm_rrc_kmax() { return RRC_KMAX; }
 

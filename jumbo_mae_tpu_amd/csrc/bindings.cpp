@@ -785,6 +785,30 @@ torch::Tensor rrc_resize(torch::Tensor src, torch::Tensor tab, int64_t size, int
   return out;
 }
 
+// Pillow-exact validation transform (Resize bicubic -> CenterCrop) of a padded batch on the device
+// (data/loader.py DeviceValidParams / collate_valid_packed): tab = [B, 18] int64 descriptors
+// (csrc/augment.hip: the 13 columns above + the full output size, the window origin and the pad
+// flag); pad rows come out as 255.  tmp_bytes / tmp_rows_max are 0 for a batch of pad rows only.
+torch::Tensor window_resize(torch::Tensor src, torch::Tensor tab, int64_t size, int64_t tmp_bytes,
+                            int64_t tmp_rows_max) {
+  CHECK_CUDA(src);
+  CHECK_CUDA(tab);
+  CHECK_DT(src, torch::kUInt8);
+  CHECK_DT(tab, torch::kInt64);
+  TORCH_CHECK(src.dim() == 1 && src.is_contiguous(), "window_resize: src must be a flat uint8 buffer");
+  TORCH_CHECK(tab.dim() == 2 && tab.size(1) == jm_window_tab() && tab.is_contiguous() && tab.size(0) > 0,
+              "window_resize: tab [B, ", jm_window_tab(), "] int64");
+  TORCH_CHECK(size > 0 && size <= 4096 && tmp_bytes >= 0 && tmp_rows_max >= 0 && (tmp_bytes > 0) == (tmp_rows_max > 0),
+              "window_resize: bad sizes");
+  const int B = tab.size(0);
+  auto out = torch::empty({B, 3, size, size}, src.options());
+  auto tmp = torch::empty({tmp_bytes > 0 ? tmp_bytes : 1}, src.options());
+  check_rc(jm_window_resize(src.data_ptr<uint8_t>(), tab.data_ptr<int64_t>(), B, (int)size, tmp.data_ptr<uint8_t>(),
+                            (int)tmp_rows_max, out.data_ptr<uint8_t>(), stream()),
+           "window_resize");
+  return out;
+}
+
 // RandAugment / AutoAugment / ColorJitter op chains on the resized batch (csrc/augment_chain.hip):
 // images uint8 [B, 3, S, S] (rrc_resize's result; CONSUMED -- it is one of the two ping-pong
 // buffers), chain float64 [B, slots, P] records (data/autoaugment.py), scratch the other buffer.
@@ -1115,6 +1139,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rrc_resize", &rrc_resize, py::arg("src"), py::arg("tab"), py::arg("size"), py::arg("tmp_bytes"),
         py::arg("tmp_rows_max"));
   m.def("rrc_kmax", &jm_rrc_kmax);
+  m.def("window_resize", &window_resize, py::arg("src"), py::arg("tab"), py::arg("size"), py::arg("tmp_bytes"),
+        py::arg("tmp_rows_max"));
+  m.def("window_tab", &jm_window_tab);
   m.def("aug_chain", &aug_chain, py::arg("images"), py::arg("chain"), py::arg("scratch"));
   m.def("gelu_drop", &gelu_drop, py::arg("a"), py::arg("b") = py::none(), py::arg("seed"), py::arg("rate"));
   m.def("softmax_dropout_fwd", &softmax_dropout_fwd);

@@ -272,6 +272,16 @@ int jm_debug_line_dropout();
 // random-resized-crop: the crop windows of src (table tab) resized to out [B, 3, S, S] uint8
 int jm_rrc_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t* tmp, int tmp_rows_max, uint8_t* out,
                   hipStream_t st);
+// window resize (the validation transform Resize -> CenterCrop): out [B, 3, S, S] uint8 = per image
+// the S x S window of a larger resize, or 255 for a pad row.  tab: int64 [B, jm_window_tab()] --
+// columns 0 .. 12 as jm_rrc_resize's (src offset, window rows / cols, window origin y0 / x0, image
+// H / W, box i / j / h / w, flip, tmp offset), 13 / 14 the full resize's output rows / columns,
+// 15 / 16 the window's origin (row, column) in that output, 17 the pad flag (augment.hip, top).
+// tmp_rows_max 0: a batch of pad rows only (src and tmp are not read)
+int jm_window_resize(const uint8_t* src, const int64_t* tab, int B, int S, uint8_t* tmp, int tmp_rows_max,
+                     uint8_t* out, hipStream_t st);
+// columns of its table
+int jm_window_tab();
 // the most filter taps per output pixel that the resize kernels take
 int jm_rrc_kmax();
 int jm_debug_line_augment();

@@ -20,6 +20,12 @@ Reference ``create_dataloaders`` (/root/reference/src/dataset.py:100-161) with h
   chain of op records per image, which csrc/augment_chain.hip applies after the resize, bit-exact
   to PIL (data/augment_ref.py is the NumPy mirror).  AugMix, random erasing and the ``src`` /
   ``none`` crops stay on the host.
+* Device validation (``create_dataloaders(device_valid=True)``; the drivers: ``--device-augment
+  auto|on`` on a GPU, ``train/common.py use_device_valid``): the validation transform Resize ->
+  CenterCrop is an S x S window of a larger resize, which the same kernels compute from an
+  18-column descriptor (``DeviceValidParams``); ``collate_valid_packed`` pads the last batch with
+  fill entries that the kernel writes as 255 (labels -1), like ``collate_and_pad``.  Bit-exact to
+  PIL; only offered while ``int(size / test_crop_ratio) >= size`` (``device_valid_ok``).
 Per-rank split replaces the reference's per-host split (one process per GPU here).
 """
 
@@ -40,12 +46,14 @@ from . import shards as S
 from .transforms import RandomResizedCrop, create_transforms
 
 RRC_TAB = 13  # csrc/augment.hip descriptor width
+WIN_TAB = 18  # ... of the window resize (validation): + full output rows / cols, window origin, pad flag
 RRC_KMAX = 24  # csrc/augment.hip taps per output pixel
 
 
 class PackedImages(NamedTuple):
     """A batch for the device augment: concatenated HWC uint8 crop windows + [B, 13] descriptors
-    (csrc/augment.hip), the scratch size of the horizontal pass and the output size; ``chain``:
+    (csrc/augment.hip; [B, 18] for a validation batch, whose pad rows have no window), the scratch
+    size of the horizontal pass and the output size; ``chain``:
     float64 [B, slots, AUG_P] op records applied after the resize (csrc/augment_chain.hip), or None."""
     src: torch.Tensor
     tab: torch.Tensor
@@ -115,6 +123,75 @@ class DeviceTrainParams(DeviceRRCParams):
         return win, desc, np.stack(recs)
 
 
+def device_valid_ok(args) -> bool:
+    """The device path covers the validation transform: the centre crop lies inside the resized
+    image (a crop that reaches outside it, which PIL pads with black, stays on the host)."""
+    return int(args.image_size / args.test_crop_ratio) >= args.image_size
+
+
+class DeviceValidParams:
+    """Worker side of the device validation transform, in place of Resize(int(size / ratio),
+    bicubic) + CenterCrop(size) + PILToArray (no random draws): ``Resize``'s output size and
+    ``CenterCrop``'s origin, the window of source pixels that the two passes read for that S x S
+    window of the full resize, and its 18-column descriptor (csrc/augment.hip).  An image too large
+    for the kernel's tap budget is resized here with PIL and shipped as an identity window."""
+
+    def __init__(self, size: int, test_crop_ratio: float = 0.875):
+        self.size = size
+        self.resize = int(size / test_crop_ratio)
+        if self.resize < size:
+            raise ValueError(f"device validation transform: Resize({self.resize}) is smaller than the crop ({size})")
+
+    def __call__(self, img):
+        from PIL import Image
+
+        from .resample_ref import read_range
+        if img.mode != "RGB":
+            img = img.convert("RGB")
+        W, H = img.size
+        S, R = self.size, self.resize
+        if W <= H:  # transforms.Resize
+            nw, nh = R, int(R * H / W)
+        else:
+            nh, nw = R, int(R * W / H)
+        i0 = int(round((nh - S) / 2.0))  # transforms.CenterCrop
+        j0 = int(round((nw - S) / 2.0))
+        if max(_taps(H, nh), _taps(W, nw)) > RRC_KMAX:
+            arr = np.asarray(img.resize((nw, nh), Image.BICUBIC))
+            H, W = nh, nw
+        else:
+            arr = np.asarray(img)
+        y0, y1 = read_range(H, 0, H, nh, i0, S)
+        x0, x1 = read_range(W, 0, W, nw, j0, S)
+        win = np.ascontiguousarray(arr[y0:y1, x0:x1])
+        return win, np.array([0, y1 - y0, x1 - x0, y0, x0, H, W, 0, 0, H, W, 0, 0, nh, nw, i0, j0, 0], dtype=np.int64)
+
+
+def collate_valid_packed(batch, batch_size: int = 1, size: int = 224):
+    """Device-validation collate, ``collate_and_pad`` for ``DeviceValidParams`` items ((window,
+    descriptor), label): windows concatenated with their offsets written into the descriptors, then
+    pad entries (no window, fill flag: the kernel writes 255) and labels -1 up to ``batch_size``.
+    Returns (PackedImages, labels)."""
+    descs = [np.asarray(d) for (_, d), _ in batch]
+    for d in descs:
+        if d.shape != (WIN_TAB,) or d.dtype != np.int64:
+            raise ValueError(f"validation descriptor must be int64 [{WIN_TAB}], got {d.dtype} {d.shape}")
+    wins = [np.asarray(w) for (w, _), _ in batch]
+    for w, d in zip(wins, descs):
+        if w.dtype != np.uint8 or w.size != d[1] * d[2] * 3:
+            raise ValueError(f"validation window must be uint8 [{d[1]}, {d[2]}, 3], got {w.dtype} {w.shape}")
+    pad = np.zeros(WIN_TAB, np.int64)
+    pad[17] = 1
+    tab = np.stack(descs + [pad] * (batch_size - len(batch)))
+    sizes = np.array([w.size for w in wins] + [0] * (batch_size - len(batch)), dtype=np.int64)
+    tab[:, 0] = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    rows = tab[:, 1]
+    tab[:, 12] = np.concatenate([[0], np.cumsum(rows * size * 3)[:-1]])
+    src = torch.from_numpy(np.concatenate([w.reshape(-1) for w in wins]))
+    labels = torch.tensor([lb for _, lb in batch] + [-1] * (batch_size - len(batch)))
+    return PackedImages(src, torch.from_numpy(tab), int((rows * size * 3).sum()), int(rows.max()), size), labels
+
+
 def check_chain(chain: np.ndarray) -> np.ndarray:
     """Host-side validation of a [B, slots, AUG_P] record table: known kinds and resample modes only."""
     from .autoaugment import AUG_KINDS, AUG_P, K_AFFINE
@@ -154,12 +231,14 @@ def collate_packed(batch, repeats: int = 1, size: int = 224):
 
 def unpack_on_device(p: PackedImages, device) -> torch.Tensor:
     """uint8 [B, 3, S, S] from a packed batch: H2D of the windows, then the resize / flip kernels
-    and, for a batch with an op chain, the chain kernels -- all on the current stream."""
+    (by the table's width: the random-resized-crop or the validation window resize) and, for a
+    batch with an op chain, the chain kernels -- all on the current stream."""
     from ..ops import _ext
     ext = _ext.load(True)
     src = p.src.to(device, non_blocking=True)
     tab = p.tab.to(device, non_blocking=True)
-    out = ext.rrc_resize(src, tab, p.size, p.tmp_bytes, p.rows_max)
+    resize = ext.window_resize if p.tab.shape[1] == WIN_TAB else ext.rrc_resize
+    out = resize(src, tab, p.size, p.tmp_bytes, p.rows_max)
     if p.chain is not None and p.chain.shape[1] > 0:
         out = ext.aug_chain(out, p.chain.to(device, non_blocking=True), torch.empty_like(out))
     return out
@@ -348,11 +427,13 @@ class ShardDataset(IterableDataset):
             epoch += 1
 
 
-def create_dataloaders(args, rank: int = 0, world: int = 1, start_batches: int = 0, device_augment: bool = False):
+def create_dataloaders(args, rank: int = 0, world: int = 1, start_batches: int = 0, device_augment: bool = False,
+                       device_valid: bool = False):
     """Returns (train_loader | None, valid_loader | None) like dataset.py:100-161.  ``start_batches``
     (resume): train batches already consumed on this rank -- the stream continues after them.
     ``device_augment``: train batches are ``PackedImages`` for ``unpack_on_device`` (requires
-    ``device_augment_ok(args)``)."""
+    ``device_augment_ok(args)``).  ``device_valid``: validation batches are (``PackedImages``,
+    labels) too (requires ``device_valid_ok(args)``); ``device_augment`` alone leaves them on PIL."""
     train_t, valid_t = create_transforms(args.random_crop, args.image_size, args.auto_augment, args.color_jitter,
                                          args.random_erasing, args.test_crop_ratio)
     if device_augment:
@@ -378,11 +459,16 @@ def create_dataloaders(args, rank: int = 0, world: int = 1, start_batches: int =
                               drop_last=True, pin_memory=pin, prefetch_factor=4 if nw > 0 else None,
                               persistent_workers=nw > 0)
     if getattr(args, "valid_dataset_shards", None):
+        if device_valid:
+            assert device_valid_ok(args), "device validation: a centre crop larger than the resized image stays on the host"
+            valid_t = DeviceValidParams(args.image_size, args.test_crop_ratio)
         ds = ShardDataset(args.valid_dataset_shards, args.mode, valid_t, False, 1, 0, rank, world,
                           image_size=args.image_size)
         bs = args.valid_batch_size // world
         nw = args.valid_loader_workers
-        valid_dl = DataLoader(ds, batch_size=bs, num_workers=nw, collate_fn=partial(collate_and_pad, batch_size=bs),
+        collate = (partial(collate_valid_packed, batch_size=bs, size=args.image_size) if device_valid
+                   else partial(collate_and_pad, batch_size=bs))
+        valid_dl = DataLoader(ds, batch_size=bs, num_workers=nw, collate_fn=collate,
                               drop_last=False, pin_memory=pin, prefetch_factor=4 if nw > 0 else None,
                               persistent_workers=nw > 0)
     return train_dl, valid_dl

@@ -106,7 +106,10 @@ def _extensions(p: argparse.ArgumentParser):
                    help="train transform on the GPU, bit-exact to PIL: RandomResizedCrop + flip and, with 'on', "
                         "RandAugment (rand-*) / AutoAugment policies / --color-jitter after it (auto: on a GPU when the "
                         "train transform is RandomResizedCrop + flip only -- the pretraining presets; on: an error "
-                        "for AugMix, --random-erasing > 0 and --random-crop src|none, which stay on the host)")
+                        "for AugMix, --random-erasing > 0 and --random-crop src|none, which stay on the host).  "
+                        "auto and on also run the validation transform (Resize + CenterCrop) on the GPU, bit-exact "
+                        "to PIL, while int(image_size / test_crop_ratio) >= image_size; off keeps everything in "
+                        "the loader workers")
     g.add_argument("--log-file-only", action="store_true", help="never use wandb even if installed")
     g.add_argument("--trace-ranges", action="store_true", help="roctx ranges per step phase (rocprofv3 --marker-trace)")
     g.add_argument("--hip-graph", action="store_true",

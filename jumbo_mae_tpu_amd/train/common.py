@@ -76,6 +76,21 @@ def use_device_augment(args, device) -> bool:
     return True
 
 
+def use_device_valid(args, device) -> bool:
+    """--device-augment auto | on also runs the validation transform (Resize -> CenterCrop) on the
+    GPU -- bit-exact to PIL, so no metric changes: on a GPU with the extension, with validation
+    shards, while the centre crop lies inside the resized image (``device_valid_ok``).  Raises for
+    nothing: what it does not cover stays on the host."""
+    from ..data.loader import device_valid_ok
+    mode = getattr(args, "device_augment", "off")
+    if mode == "off" or device.type != "cuda" or not getattr(args, "valid_dataset_shards", None):
+        return False
+    if not device_valid_ok(args):
+        return False
+    from ..ops import _ext
+    return bool(_ext.available())
+
+
 class DevicePrefetcher:
     """Moves the next host batch to the device on a side stream while the current step runs; a
     device-augment batch (data/loader.py ``PackedImages``) is resized / flipped there too."""

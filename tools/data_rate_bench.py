@@ -9,11 +9,18 @@ training rate.  Shards are written with real JPEG files at ImageNet-like sizes
     python tools/data_rate_bench.py [--workers 1,2,4,8] [--mode pretrain|finetune] [--batch 256]
                                     [--h2d] [--device-augment]
                                     [--auto-augment SPEC] [--color-jitter X] [--random-erasing P]
+    python tools/data_rate_bench.py --valid [--workers 1,8] [--device-augment] [--h2d]
 
 The augment flags override the mode's transform, so that the PIL and the device path can be
 measured per worker on one box with the same transform -- the config/ft.sh one is
 ``--mode finetune --auto-augment rand-m9-mstd0.5-inc1 --color-jitter 0 --random-erasing 0``
 (``--device-augment`` then runs RandAugment on the GPU too, csrc/augment_chain.hip).
+
+``--valid``: the validation loader over the same shards (Resize(256, bicubic) + CenterCrop(224),
+padded final batch), PIL in the workers or -- with ``--device-augment`` -- decode-only workers and
+the window resize on the GPU (csrc/augment.hip).  A validation pass is finite, so the rate is
+images / wall time of whole passes (one untimed pass first: worker start-up, shard cache), the
+refill of the workers' prefetch queues at the start of each pass included.
 
 Prints one JSON line per worker count: steady-state images/s of the loader (after draining what
 the workers prefetched), per worker, and with ``--h2d`` the rate through the DevicePrefetcher
@@ -50,6 +57,43 @@ def loader_args(spec: str, mode: str, batch: int, workers: int, auto_augment=Non
         valid_loader_workers=0)
 
 
+def valid_rows(a, spec, mean_kb):
+    """--valid: whole validation passes, PIL or device transform, per worker count."""
+    images = a.shards * a.per_shard
+    for nw in [int(x) for x in a.workers.split(",")]:
+        largs = loader_args(None, "finetune", a.batch, 0)
+        largs.valid_dataset_shards, largs.valid_loader_workers = spec, nw
+        out = {"mode": "valid", "device_augment": a.device_augment, "workers": nw, "batch": a.batch,
+               "images_per_pass": images, "jpeg_kb": round(mean_kb, 1), "cpus": os.cpu_count()}
+
+        def passes(wrap, k=3):
+            _, dl = create_dataloaders(largs, device_valid=a.device_augment)
+            n, last = 0, None
+            for last in wrap(dl):  # untimed
+                n += last[1].numel()
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(k):
+                for last in wrap(dl):
+                    pass
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+            return k * images / (time.perf_counter() - t0), n, last
+
+        rate, n, b = passes(iter)
+        out.update(images_per_sec=round(rate, 1), per_worker=round(rate / max(nw, 1), 1), padded_images_per_pass=n)
+        if a.device_augment:
+            out["window_kb_per_image"] = round(b[0].src.numel() / int((b[1] != -1).sum()) / 1024, 1)
+        if a.h2d and torch.cuda.is_available():
+            from jumbo_mae_tpu_amd.train.common import DevicePrefetcher
+            dev = torch.device("cuda:0")
+            rate, _, x = passes(lambda dl: DevicePrefetcher(dl, dev))
+            out["prefetcher_images_per_sec"] = round(rate, 1)
+            out["device_shape"] = list(x[0].shape)
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", default="/tmp/jmae_jpeg_shards")
@@ -64,6 +108,9 @@ def main():
     ap.add_argument("--auto-augment", default=None, help="train transform override (default: the mode's)")
     ap.add_argument("--color-jitter", type=float, default=None)
     ap.add_argument("--random-erasing", type=float, default=None)
+    ap.add_argument("--valid", action="store_true",
+                    help="the validation loader (Resize + CenterCrop) over the same shards; with --device-augment "
+                         "the transform runs on the GPU")
     a = ap.parse_args()
     aug = dict(auto_augment=a.auto_augment, color_jitter=a.color_jitter, random_erasing=a.random_erasing)
     spec = os.path.join(a.dir, f"train-{{000000..{a.shards - 1:06d}}}.tar")
@@ -73,6 +120,9 @@ def main():
         print(f"[data] wrote {a.shards} x {a.per_shard} JPEGs in {time.time() - t0:.1f}s", file=sys.stderr)
     sizes = [os.path.getsize(os.path.join(a.dir, f"train-{i:06d}.tar")) for i in range(a.shards)]
     mean_kb = sum(sizes) / (a.shards * a.per_shard) / 1024
+    if a.valid:
+        return valid_rows(a, spec, mean_kb)
+
     def steady(it, nw, batch):
         """Steady-state images/s: first drain what the workers prefetched before the clock starts
         (up to nw x prefetch_factor batches), then time 6x that many batches (a backlog refilled
