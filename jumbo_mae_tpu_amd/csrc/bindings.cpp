@@ -1179,6 +1179,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "2 = 4-phase kernels at every M without tail split (rows = forced tile height)");
   m.def("gemm_nt_tiles", &jm_gemm_nt_tiles, py::arg("M"), py::arg("N"), py::arg("K") = 1024, py::arg("epi") = 0,
         py::arg("lda") = 0, "output tiles (workgroups before split-K) of an NT launch");
+  m.def(
+      "gemm_nt_tail_plan",
+      [](int M, int N, int K, int epi, long lda) {
+        int r = 0;
+        long n = 0;
+        const int S = jm_gemm_nt_tail_plan(M, N, K, epi, lda, &r, &n);
+        return std::make_pair(S, r);
+      },
+      py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi") = 0, py::arg("lda") = 0,
+      "(S, tail tiles) of the tail split of an NT launch (S = 0: none); read-only");
   m.def("transpose_bf16_batch", &transpose_bf16_batch);
   m.def("gemm_nt_splitk", &gemm_nt_splitk, py::arg("A"), py::arg("B"), py::arg("bias") = py::none(),
         py::arg("splits") = 8, py::arg("add") = py::none());

@@ -5,6 +5,8 @@ import math
 import pytest
 import torch
 
+from gemm_ref import gd_check as _gd_check
+
 pytestmark = pytest.mark.gpu
 
 
@@ -289,18 +291,6 @@ def test_gemm_nt_short_rows(ext, M, N, K, lda, rows):
         r = dg * fac
         assert rel(o, r) < 1e-2, deriv
         assert rel(db - 0.25, r.sum(0)) < 1e-2, deriv
-
-
-def _gd_check(dq, dref):
-    """uint8 gelu' codes of the fused FF1 forward (csrc/common.h gd_code) against the fp32 derivative
-    of the same bf16 pre-activation: the torch mirror's code up to one step (fma vs two roundings at
-    exact ties), the decoded value within half a step.  Returns the decoded fp32 gelu'."""
-    from jumbo_mae_tpu_amd.ops import prims as P
-    assert dq.dtype == torch.uint8 and dq.shape == dref.shape
-    assert (dq.int() - P.gd_encode(dref).int()).abs().max().item() <= 1
-    d = P.gd_decode(dq, dtype=torch.float32)
-    assert (d - dref).abs().max().item() <= 0.5 / P.GD_Q + 1e-4
-    return d
 
 
 def test_gemm_tile_rows_choice(ext):
