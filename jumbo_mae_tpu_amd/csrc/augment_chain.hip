@@ -1,5 +1,6 @@
-// Device-side RandAugment / AutoAugment / ColorJitter on the uint8 [B, 3, S, S] output of rrc_resize
-// (csrc/augment.hip), BIT-EXACT to the PIL calls of data/autoaugment.py (gfx950).
+// Device-side RandAugment / AutoAugment / AugMix / ColorJitter / RandomErasing on the uint8
+// [B, 3, S, S] output of rrc_resize (csrc/augment.hip), BIT-EXACT to the PIL calls of
+// data/autoaugment.py and data/transforms.py (gfx950).
 //
 // The loader worker makes the transform's random draws and ships, per image, a chain of op records
 // (data/autoaugment.py op_record; data/loader.py DeviceTrainParams).  The chain is applied slot by
@@ -23,6 +24,10 @@
 // Record (double x AUG_P): kind, argument (bits / threshold / add / blend factor), affine
 // coefficients m0..m5, resample (2 bilinear, 3 bicubic), fill r, g, b.  A kind the device does not
 // know (the host rejects it in collate) is an identity copy, never an out-of-range access.
+//
+// AugMix runs its W chains as one op chain over a [B * W] batch of replicas and composites them with
+// augmix_mix_kernel; RandomErasing's noise is drawn by the worker (np.random, so the PIL path's
+// bytes) and pasted by erase_paste_kernel.  Both are documented at the kernels below.
 #include "common.h"
 #include "jm_api.h"
 
@@ -292,6 +297,111 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const uint8_t* __restric
   }
 }
 
+// ---- AugMix mixing and random erasing (data/autoaugment.py AugMix, data/transforms.py RandomErasing)
+constexpr int MIX_WMAX = 8;
+constexpr int ERASE_TILE = 2048;
+
+template <int NB> struct ByteVec;
+template <> struct ByteVec<1> { using T = uint8_t; };
+template <> struct ByteVec<4> { using T = uint32_t; };
+template <> struct ByteVec<16> { using T = uint4; };
+
+template <int NB> JM_DEVICE void load_bytes(const uint8_t* p, uint8_t* v) {
+  const typename ByteVec<NB>::T t = *reinterpret_cast<const typename ByteVec<NB>::T*>(p);
+  __builtin_memcpy(v, &t, NB);
+}
+
+template <int NB> JM_DEVICE void store_bytes(uint8_t* p, const uint8_t* v) {
+  typename ByteVec<NB>::T t;
+  __builtin_memcpy(&t, v, NB);
+  *reinterpret_cast<typename ByteVec<NB>::T*>(p) = t;
+}
+
+// AugMix's composite of an image with its W augmented chains.  block (tile of 256 x NB bytes, image),
+// thread = NB consecutive bytes of the image's 3 S S (n3): one NB-byte load from the original and
+// from each chain, one NB-byte store.  NB is the widest of 16 / 4 / 1 that divides n3 and every base
+// pointer (the launcher picks it), so every image's and chain's offset is aligned and no thread
+// straddles the end of an image: NB = 1 is the scalar path of an odd S.
+//   table float [B, W + 1].  Not blended: the weights w_k and m --
+//     mixed = 0; mixed = mixed + w_k * x_k (float32, multiply and add rounded separately, chain
+//     order); clip to [0, 255], truncate; Image.blend(original, mixed, m).
+//   Blended: the alphas a_k in application order -- img = Image.blend(img, x_k, a_k), rounded to a
+//     byte after every step.
+template <int NB>
+__global__ __launch_bounds__(256) void augmix_mix_kernel(const uint8_t* __restrict__ orig,
+                                                         const uint8_t* __restrict__ chains,
+                                                         const float* __restrict__ table, uint8_t* __restrict__ out,
+                                                         int W, int blended, long n3) {
+  JM_DGUARD(blockDim.x == 256 && W >= 1 && W <= MIX_WMAX && n3 % NB == 0);
+  const int b = blockIdx.y;
+  const long e = ((long)blockIdx.x * 256 + threadIdx.x) * NB;
+  if (e >= n3) return;
+  const float* tb = table + (long)b * (W + 1);
+  const uint8_t* xb = chains + (long)b * W * n3 + e;
+  uint8_t o[NB], x[NB], r[NB];
+  load_bytes<NB>(orig + (long)b * n3 + e, o);
+  if (blended) {
+#pragma unroll
+    for (int q = 0; q < NB; ++q) r[q] = o[q];
+    for (int k = 0; k < W; ++k) {
+      const float a = tb[k];
+      const bool trunc_only = a >= 0.f && a <= 1.f;
+      load_bytes<NB>(xb + (long)k * n3, x);
+#pragma unroll
+      for (int q = 0; q < NB; ++q) r[q] = blend8(r[q], x[q], a, trunc_only);
+    }
+  } else {
+    float acc[NB];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) acc[q] = 0.f;
+    for (int k = 0; k < W; ++k) {
+      const float w = tb[k];
+      load_bytes<NB>(xb + (long)k * n3, x);
+#pragma unroll
+      for (int q = 0; q < NB; ++q) acc[q] = acc[q] + w * (float)x[q];
+    }
+    const float m = tb[W];
+    const bool trunc_only = m >= 0.f && m <= 1.f;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const int mixed = acc[q] >= 255.f ? 255 : (acc[q] > 0.f ? (int)acc[q] : 0);  // NaN -> 0
+      r[q] = blend8(o[q], mixed, m, trunc_only);
+    }
+  }
+  store_bytes<NB>(out + (long)b * n3 + e, r);
+}
+
+// RandomErasing's paste, in place.  block (tile of ERASE_TILE bytes of the box, image); table int64
+// [B, 5]: box row i, column j, rows eh, columns ew, offset of its [3, eh, ew] fill bytes in ``fill``.
+// eh == 0: the image is not erased.  A record that does not describe a box inside the image with its
+// bytes inside ``fill`` (the host rejects it in collate) erases nothing, so no record can make this
+// kernel read or write out of bounds.
+__global__ __launch_bounds__(256) void erase_paste_kernel(uint8_t* __restrict__ images,
+                                                          const int64_t* __restrict__ table,
+                                                          const uint8_t* __restrict__ fill, long fill_len, int S) {
+  JM_DGUARD(blockDim.x == 256);
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int64_t* t = table + (long)b * 5;
+  const int64_t i = t[0], j = t[1], eh = t[2], ew = t[3], off = t[4];
+  if (eh == 0) return;  // workgroup-uniform
+  const bool ok = eh > 0 && eh < S && ew > 0 && ew < S && i >= 0 && i <= S - eh && j >= 0 && j <= S - ew && off >= 0 &&
+                  off <= fill_len - 3 * eh * ew;
+  JM_DASSERT(ok);
+  if (!ok) return;  // workgroup-uniform
+  const int w = (int)ew, area = (int)eh * w, nb = 3 * area;
+  const int p0 = blockIdx.x * ERASE_TILE;
+  if (p0 >= nb) return;  // the grid covers the largest box of the batch
+  const int p1 = min(nb, p0 + ERASE_TILE);
+  const long n = (long)S * S;
+  const uint8_t* fb = fill + off;
+  uint8_t* ob = images + (long)b * 3 * n + (long)i * S + j;
+  for (int p = p0 + tid; p < p1; p += 256) {
+    const int c = p / area, q = p - c * area;
+    const int y = q / w, x = q - y * w;
+    ob[(long)c * n + (long)y * S + x] = fb[p];
+  }
+}
+
 }  // namespace
 
 int jm_aug_stat_words() { return AUG_STAT_WORDS; }
@@ -314,6 +424,40 @@ int jm_aug_chain(uint8_t* images, uint8_t* scratch, const double* chain, int B, 
     dst = t;
   }
   return src == images ? 0 : 1;
+}
+
+// orig / out: uint8 [B, 3, S, S]; chains: uint8 [B * W, 3, S, S], chain k of image b at b * W + k;
+// table: float [B, W + 1] (augmix_mix_kernel).  out must not alias an input.  Stream-ordered.
+int jm_augmix_mix(const uint8_t* orig, const uint8_t* chains, const float* table, uint8_t* out, int B, int W, int S,
+                  int blended, hipStream_t st) {
+  if (B <= 0 || B > 65535 || W < 1 || W > MIX_WMAX || S <= 0 || S > 4096) return -1;
+  const long n3 = 3L * S * S;
+  const uintptr_t al = (uintptr_t)orig | (uintptr_t)chains | (uintptr_t)out | (uintptr_t)n3;
+  if ((al & 15) == 0) {
+    augmix_mix_kernel<16><<<dim3((unsigned)((n3 / 16 + 255) / 256), B), 256, 0, st>>>(orig, chains, table, out, W,
+                                                                                      blended, n3);
+  } else if ((al & 3) == 0) {
+    augmix_mix_kernel<4><<<dim3((unsigned)((n3 / 4 + 255) / 256), B), 256, 0, st>>>(orig, chains, table, out, W,
+                                                                                    blended, n3);
+  } else {
+    augmix_mix_kernel<1><<<dim3((unsigned)((n3 + 255) / 256), B), 256, 0, st>>>(orig, chains, table, out, W, blended,
+                                                                                n3);
+  }
+  return 0;
+}
+
+// images: uint8 [B, 3, S, S], erased in place; table: int64 [B, 5]; fill: fill_len bytes
+// (erase_paste_kernel).  box_bytes_max: the largest 3 eh ew of the batch's boxes, which sizes the
+// grid (0: the largest box there can be, 3 (S - 1)^2).  Stream-ordered.
+int jm_erase_paste(uint8_t* images, const int64_t* table, const uint8_t* fill, long fill_len, int B, int S,
+                   long box_bytes_max, hipStream_t st) {
+  if (B <= 0 || B > 65535 || S <= 0 || S > 4096 || fill_len < 0 || box_bytes_max < 0) return -1;
+  const long limit = 3L * (S - 1) * (S - 1);
+  const long bytes = box_bytes_max == 0 || box_bytes_max > limit ? limit : box_bytes_max;
+  if (bytes == 0) return 0;  // S == 1: no box fits
+  erase_paste_kernel<<<dim3((unsigned)((bytes + ERASE_TILE - 1) / ERASE_TILE), B), 256, 0, st>>>(images, table, fill,
+                                                                                                fill_len, S);
+  return 0;
 }
 
 JM_DEBUG_EXPORT(augment_chain)

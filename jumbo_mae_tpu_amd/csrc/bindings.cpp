@@ -837,6 +837,62 @@ torch::Tensor aug_chain(torch::Tensor images, torch::Tensor chain, torch::Tensor
   return rc == 1 ? scratch : images;
 }
 
+// AugMix's composite (csrc/augment_chain.hip augmix_mix_kernel): orig uint8 [B, 3, S, S] (the resized
+// batch), chains uint8 [B * W, 3, S, S] (aug_chain's result on the W replicas of every image, chain
+// k of image b at b * W + k), table float32 [B, W + 1] (data/autoaugment.py AugMix.describe).
+// Returns a new [B, 3, S, S]; the inputs are left as they are.  Stream-ordered, no host sync.
+torch::Tensor augmix_mix(torch::Tensor orig, torch::Tensor chains, torch::Tensor table, bool blended) {
+  CHECK_CUDA(orig);
+  CHECK_CUDA(chains);
+  CHECK_CUDA(table);
+  CHECK_DT(orig, torch::kUInt8);
+  CHECK_DT(chains, torch::kUInt8);
+  CHECK_DT(table, torch::kFloat32);
+  TORCH_CHECK(orig.dim() == 4 && orig.size(1) == 3 && orig.size(2) == orig.size(3) && orig.is_contiguous(),
+              "augmix_mix: orig must be contiguous uint8 [B, 3, S, S]");
+  TORCH_CHECK(orig.size(0) > 0 && orig.size(0) <= 65535 && orig.size(2) > 0 && orig.size(2) <= 4096,
+              "augmix_mix: bad sizes");
+  TORCH_CHECK(table.dim() == 2 && table.size(0) == orig.size(0) && table.size(1) >= 2 && table.size(1) <= 9 &&
+                  table.is_contiguous(),
+              "augmix_mix: table must be contiguous float32 [B, W + 1] with 1 <= W <= 8");
+  const int64_t B = orig.size(0), W = table.size(1) - 1, S = orig.size(2);
+  TORCH_CHECK(chains.dim() == 4 && chains.size(0) == B * W && chains.size(1) == 3 && chains.size(2) == S &&
+                  chains.size(3) == S && chains.is_contiguous(),
+              "augmix_mix: chains must be contiguous uint8 [B * W, 3, S, S]");
+  auto out = torch::empty_like(orig);
+  check_rc(jm_augmix_mix(orig.data_ptr<uint8_t>(), chains.data_ptr<uint8_t>(), table.data_ptr<float>(),
+                         out.data_ptr<uint8_t>(), (int)B, (int)W, (int)S, blended ? 1 : 0, stream()),
+           "augmix_mix");
+  return out;
+}
+
+// RandomErasing's paste (csrc/augment_chain.hip erase_paste_kernel), in place on images uint8
+// [B, 3, S, S]: table int64 [B, 5] = box row, column, rows, columns (rows 0: not erased) and the
+// offset of the box's [3, rows, columns] bytes in the flat uint8 fill (data/loader.py
+// collate_packed).  box_bytes_max: the largest 3 * rows * columns of the table, from its host copy
+// (0: unknown).  Returns images.  Stream-ordered, no host sync.
+torch::Tensor erase_paste(torch::Tensor images, torch::Tensor table, torch::Tensor fill, int64_t box_bytes_max) {
+  CHECK_CUDA(images);
+  CHECK_CUDA(table);
+  CHECK_CUDA(fill);
+  CHECK_DT(images, torch::kUInt8);
+  CHECK_DT(table, torch::kInt64);
+  CHECK_DT(fill, torch::kUInt8);
+  TORCH_CHECK(images.dim() == 4 && images.size(1) == 3 && images.size(2) == images.size(3) && images.is_contiguous(),
+              "erase_paste: images must be contiguous uint8 [B, 3, S, S]");
+  TORCH_CHECK(images.size(0) > 0 && images.size(0) <= 65535 && images.size(2) > 0 && images.size(2) <= 4096,
+              "erase_paste: bad sizes");
+  TORCH_CHECK(table.dim() == 2 && table.size(0) == images.size(0) && table.size(1) == 5 && table.is_contiguous(),
+              "erase_paste: table must be contiguous int64 [B, 5]");
+  TORCH_CHECK(fill.dim() == 1 && fill.is_contiguous(), "erase_paste: fill must be a flat uint8 buffer");
+  TORCH_CHECK(box_bytes_max >= 0, "erase_paste: box_bytes_max < 0");
+  check_rc(jm_erase_paste(images.data_ptr<uint8_t>(), table.data_ptr<int64_t>(),
+                          fill.numel() ? fill.data_ptr<uint8_t>() : nullptr, (long)fill.numel(), (int)images.size(0),
+                          (int)images.size(2), (long)box_bytes_max, stream()),
+           "erase_paste");
+  return images;
+}
+
 // ---------------------------------------------------------------- dropout (csrc/dropout.hip)
 
 // y = x * keep(seed, i) / keep  (bf16 or fp32, contiguous, numel % 8 == 0); also its own backward
@@ -1143,6 +1199,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tmp_rows_max"));
   m.def("window_tab", &jm_window_tab);
   m.def("aug_chain", &aug_chain, py::arg("images"), py::arg("chain"), py::arg("scratch"));
+  m.def("augmix_mix", &augmix_mix, py::arg("orig"), py::arg("chains"), py::arg("table"), py::arg("blended"));
+  m.def("erase_paste", &erase_paste, py::arg("images"), py::arg("table"), py::arg("fill"),
+        py::arg("box_bytes_max") = 0);
   m.def("gelu_drop", &gelu_drop, py::arg("a"), py::arg("b") = py::none(), py::arg("seed"), py::arg("rate"));
   m.def("softmax_dropout_fwd", &softmax_dropout_fwd);
   m.def("softmax_dropout_bwd", &softmax_dropout_bwd);

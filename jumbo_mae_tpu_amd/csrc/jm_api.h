@@ -294,4 +294,12 @@ int jm_aug_record_len();
 // the RandAugment op chain of every image on the ping-pong buffers; returns the buffer with the result (0 / 1)
 int jm_aug_chain(uint8_t* images, uint8_t* scratch, const double* chain, int B, int slots, int S, uint32_t* stats,
                  hipStream_t st);
+// AugMix: out [B, 3, S, S] = the composite of orig with its W chain results (chains [B * W, 3, S, S],
+// chain k of image b at b * W + k) by table float [B, W + 1]: weights and m, or (blended) the alphas
+int jm_augmix_mix(const uint8_t* orig, const uint8_t* chains, const float* table, uint8_t* out, int B, int W, int S,
+                  int blended, hipStream_t st);
+// RandomErasing in place: table int64 [B, 5] = box i, j, eh, ew (eh 0: none) and the offset of its
+// [3, eh, ew] bytes in fill; box_bytes_max: the batch's largest 3 eh ew (0: unknown, the largest possible)
+int jm_erase_paste(uint8_t* images, const int64_t* table, const uint8_t* fill, long fill_len, int B, int S,
+                   long box_bytes_max, hipStream_t st);
 int jm_debug_line_augment_chain();

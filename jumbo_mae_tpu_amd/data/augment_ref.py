@@ -13,6 +13,11 @@ Arithmetic, as Pillow does it:
   [0, W) x [0, H), bilinear / bicubic (a = -0.5 Catmull-Rom in Pillow's p1..p4 form) in double with
   edge-clamped neighbours.
 * ImageOps.equalize / autocontrast: per-band histogram -> lookup table.
+* AugMix (``augmix_mix``): ``mixed += w_k * chain_k`` in float32 (multiply and add rounded
+  separately), clipped and truncated, then Image.blend(original, mixed, m) -- the blend above; the
+  ``blended`` variant is a sequence of those blends.  RandomErasing (``erase_paste``): a byte copy of
+  the worker-drawn fill.  Both are pinned to PIL / the host transform in
+  tests/test_device_erase_augmix.py and are the oracle of tests/test_erase_augmix_gpu.py.
 """
 
 from __future__ import annotations
@@ -155,3 +160,35 @@ def apply_chain(images: np.ndarray, chain: np.ndarray) -> np.ndarray:
             a = apply_op(a, rec)
         out.append(a)
     return np.stack(out)
+
+
+def augmix_mix(orig: np.ndarray, chains: np.ndarray, table: np.ndarray, blended: bool) -> np.ndarray:
+    """AugMix's composite (augmix_mix_kernel): orig uint8 [B, 3, S, S], chains uint8 [B * W, 3, S, S]
+    (chain k of image b at b * W + k), table float32 [B, W + 1] (AugMix.describe).  Not blended:
+    ``mixed += w_k * chain_k`` in float32, clipped and truncated, then Image.blend(orig, mixed, m);
+    blended: Image.blend(img, chain_k, a_k) step by step."""
+    B, W = table.shape[0], table.shape[1] - 1
+    assert table.dtype == np.float32 and W >= 1 and chains.shape == (B * W, *orig.shape[1:]), (table.shape, chains.shape)
+    out = np.empty_like(orig)
+    for b in range(B):
+        if blended:
+            img = orig[b]
+            for k in range(W):
+                img = blend(img, chains[b * W + k], table[b, k])
+            out[b] = img
+            continue
+        mixed = np.zeros(orig.shape[1:], np.float32)
+        for k in range(W):
+            mixed += table[b, k] * chains[b * W + k].astype(np.float32)
+        out[b] = blend(orig[b], np.clip(mixed, 0, 255).astype(np.uint8), table[b, W])
+    return out
+
+
+def erase_paste(images: np.ndarray, table: np.ndarray, fill: np.ndarray) -> np.ndarray:
+    """RandomErasing's paste (erase_paste_kernel): images uint8 [B, 3, S, S], table int64 [B, 5] = box
+    i, j, eh, ew (eh 0: not erased) and the offset of its [3, eh, ew] bytes in the flat uint8 fill."""
+    out = images.copy()
+    for a, (i, j, eh, ew, off) in zip(out, table.tolist()):
+        if eh:
+            a[:, i:i + eh, j:j + ew] = fill[off:off + 3 * eh * ew].reshape(3, eh, ew)
+    return out

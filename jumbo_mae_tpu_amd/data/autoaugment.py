@@ -366,6 +366,25 @@ class AugMix:
         mixed = Image.fromarray(np.clip(mixed, 0, 255).astype(np.uint8))
         return Image.blend(img, mixed, m)
 
+    # device augment: every chain takes ``chain_slots`` records (identity-padded)
+    chain_slots = property(lambda self: self.depth if self.depth > 0 else 3)
+    slots = property(lambda self: self.width * self.chain_slots)
+
+    def describe(self, size: int):
+        """__call__'s draws in its order, no pixels: (``width`` x ``chain_slots`` op records, chain
+        after chain; the float32 mixing values [width + 1] of csrc/augment_chain.hip
+        augmix_mix_kernel -- the Dirichlet weights and m, or for ``blended`` the alphas of
+        ``blended_weights`` in application order and a 0)."""
+        ws = np.random.dirichlet([self.alpha] * self.width).astype(np.float32)
+        m = float(np.float32(np.random.beta(self.alpha, self.alpha)))
+        recs = []
+        for _ in range(self.width):
+            d = self.depth if self.depth > 0 else random.randint(1, 3)
+            recs += [op.describe(size) for op in random.choices(self.ops, k=d)]
+            recs += [op_record()] * (self.chain_slots - d)
+        mix = np.append(self.blended_weights(ws, m), 0.0) if self.blended else np.append(ws, m)
+        return recs, mix.astype(np.float32)
+
 
 def augmix_transform(spec: str, hparams: dict) -> AugMix:
     name, args = _parse(spec)

@@ -18,10 +18,12 @@ Reference ``create_dataloaders`` (/root/reference/src/dataset.py:100-161) with h
   ``--device-augment on`` also covers the finetune transform -- RandAugment / AutoAugment and
   ColorJitter after the crop (``DeviceTrainParams``): the worker makes their draws too and ships a
   chain of op records per image, which csrc/augment_chain.hip applies after the resize, bit-exact
-  to PIL (data/augment_ref.py is the NumPy mirror).  AugMix, random erasing and the ``src`` /
-  ``none`` crops stay on the host.
+  to PIL (data/augment_ref.py is the NumPy mirror).  ``--device-augment all`` adds AugMix (its
+  ``width`` chains run as one op chain over the replicated batch and are composited by
+  ``augmix_mix``) and random erasing (the worker draws the box and the noise bytes and ships them;
+  ``erase_paste`` writes them into the final batch).  The ``src`` / ``none`` crops stay on the host.
 * Device validation (``create_dataloaders(device_valid=True)``; the drivers: ``--device-augment
-  auto|on`` on a GPU, ``train/common.py use_device_valid``): the validation transform Resize ->
+  auto|on|all`` on a GPU, ``train/common.py use_device_valid``): the validation transform Resize ->
   CenterCrop is an S x S window of a larger resize, which the same kernels compute from an
   18-column descriptor (``DeviceValidParams``); ``collate_valid_packed`` pads the last batch with
   fill entries that the kernel writes as 255 (labels -1), like ``collate_and_pad``.  Bit-exact to
@@ -54,13 +56,21 @@ class PackedImages(NamedTuple):
     """A batch for the device augment: concatenated HWC uint8 crop windows + [B, 13] descriptors
     (csrc/augment.hip; [B, 18] for a validation batch, whose pad rows have no window), the scratch
     size of the horizontal pass and the output size; ``chain``:
-    float64 [B, slots, AUG_P] op records applied after the resize (csrc/augment_chain.hip), or None."""
+    float64 [B, slots, AUG_P] op records applied after the resize (csrc/augment_chain.hip), or None.
+    AugMix: ``mix`` float32 [B, W + 1] mixing values and the static ``mix_wdb`` = (W chains, D slots
+    each, blended); the first W * D slots of ``chain`` are the chains, the rest runs on the mixed
+    image.  Random erasing: ``erase`` int64 [B, 5] = box i, j, eh, ew (eh 0: not erased) and the
+    offset of the box's [3, eh, ew] bytes in ``fill``, one flat uint8 buffer."""
     src: torch.Tensor
     tab: torch.Tensor
     tmp_bytes: int
     rows_max: int
     size: int
     chain: torch.Tensor | None = None
+    mix: torch.Tensor | None = None
+    mix_wdb: tuple | None = None
+    erase: torch.Tensor | None = None
+    fill: torch.Tensor | None = None
 
 
 def _span(n: int, a: int, c: int, out: int) -> tuple[int, int]:
@@ -106,21 +116,39 @@ class DeviceRRCParams:
 
 class DeviceTrainParams(DeviceRRCParams):
     """Worker side of the device augment for the finetune transform: ``DeviceRRCParams``, then the
-    draws of RandAugment / AutoAugment (``aa``) and ColorJitter (``cj``) in the PIL path's order.
-    Returns (window, descriptor, chain): chain = float64 [slots, AUG_P] op records
-    (data/autoaugment.py), identity-padded to the transform's fixed slot count."""
+    draws of RandAugment / AutoAugment / AugMix (``aa``), ColorJitter (``cj``) and RandomErasing
+    (``erase``) in the PIL path's order.  Returns (window, descriptor, chain): chain = float64
+    [slots, AUG_P] op records (data/autoaugment.py), identity-padded to the transform's fixed slot
+    count.  With AugMix or erasing the item is (window, descriptor, chain, mix, box, fill): mix =
+    (float32 [W + 1] mixing values, (W, D, blended)) or None -- the chain then starts with the W
+    chains of D slots each; box int64 [4] and fill uint8 [3, eh, ew] (``RandomErasing.describe``)
+    or None."""
 
-    def __init__(self, size: int, aa=None, cj=None):
+    def __init__(self, size: int, aa=None, cj=None, erase=None):
+        from .autoaugment import AugMix
         super().__init__(size)
         self.stages = [t for t in (aa, cj) if t is not None]
         self.slots = sum(t.slots for t in self.stages)
+        self.mix_wdb = (aa.width, aa.chain_slots, int(aa.blended)) if isinstance(aa, AugMix) else None
+        if self.mix_wdb is not None and not 1 <= aa.width <= 8:
+            raise ValueError(f"device augment: AugMix with {aa.width} chains (the mix kernel takes 1 .. 8)")
+        self.erase = erase
 
     def __call__(self, img):
         from .autoaugment import op_record
         win, desc = super().__call__(img)
-        recs = [r for t in self.stages for r in t.describe(self.size)]
+        recs, mix = [], None
+        for t in self.stages:
+            d = t.describe(self.size)
+            if self.mix_wdb is not None and t is self.stages[0]:
+                d, mix = d[0], (d[1], self.mix_wdb)
+            recs += d
         recs += [op_record()] * (self.slots - len(recs))
-        return win, desc, np.stack(recs)
+        chain = np.stack(recs) if recs else np.zeros((0, len(op_record())), np.float64)
+        if mix is None and self.erase is None:
+            return win, desc, chain
+        box, fill = self.erase.describe(self.size) if self.erase is not None else (None, None)
+        return win, desc, chain, mix, box, fill
 
 
 def device_valid_ok(args) -> bool:
@@ -206,18 +234,81 @@ def check_chain(chain: np.ndarray) -> np.ndarray:
     return chain
 
 
+def check_mix(mix: np.ndarray, wdb, slots: int) -> np.ndarray:
+    """Host-side validation of an AugMix mix table against its static (W, D, blended): float32
+    [B, W + 1], finite, 1 <= W <= 8, and W * D chain slots in the batch's op chain."""
+    W, D, _ = wdb
+    if not (1 <= W <= 8 and D >= 1 and W * D <= slots):
+        raise ValueError(f"AugMix mix: {W} chains of {D} slots do not fit the device path (1..8 chains, {slots} slots)")
+    if mix.ndim != 2 or mix.shape[1] != W + 1 or mix.dtype != np.float32:
+        raise ValueError(f"AugMix mix table must be float32 [B, {W + 1}], got {mix.dtype} {mix.shape}")
+    if not np.isfinite(mix).all():
+        raise ValueError("AugMix mix table: non-finite value(s)")
+    return mix
+
+
+def check_erase(erase: np.ndarray, fill_len: int, size: int) -> np.ndarray:
+    """Host-side validation of an erase table: int64 [B, 5]; a row is all zero up to the offset (not
+    erased) or a box of 1 .. size - 1 rows and columns inside the image whose 3 * eh * ew bytes lie
+    inside the fill buffer."""
+    if erase.ndim != 2 or erase.shape[1] != 5 or erase.dtype != np.int64:
+        raise ValueError(f"erase table must be int64 [B, 5], got {erase.dtype} {erase.shape}")
+    i, j, eh, ew, off = erase.T
+    on = eh != 0
+    if ((eh < 0) | (~on & (ew != 0))).any():
+        raise ValueError("erase table: a box with negative or half-empty extent")
+    if (on & ((eh >= size) | (ew >= size) | (ew <= 0))).any():
+        raise ValueError(f"erase table: a box needs 1 .. {size - 1} rows and columns")
+    if (on & ((i < 0) | (j < 0) | (i + eh > size) | (j + ew > size))).any():
+        raise ValueError(f"erase table: a box leaves the image [0, {size})")
+    if (on & ((off < 0) | (off + 3 * eh * ew > fill_len))).any():
+        raise ValueError(f"erase table: fill bytes outside the fill buffer of {fill_len}")
+    return erase
+
+
+def _collate_mix_erase(items, slots: int, size: int):
+    """The AugMix and erasing fields of ``PackedImages`` from the (mix, box, fill) tails of the items."""
+    mix = wdb = erase = fill = None
+    if items[0][0] is not None:
+        wdb = tuple(int(v) for v in items[0][0][1])
+        if any(tuple(m[1]) != wdb for m, _, _ in items):
+            raise ValueError("AugMix mix: the items of a batch disagree on (chains, slots, blended)")
+        rows = [np.asarray(m[0]) for m, _, _ in items]
+        if any(r.shape != rows[0].shape or r.dtype != rows[0].dtype for r in rows):
+            raise ValueError(f"AugMix mix table must be float32 [B, {wdb[0] + 1}]: rows of different shape or dtype")
+        mix = torch.from_numpy(check_mix(np.stack(rows), wdb, slots))
+    if items[0][1] is not None:
+        boxes = [np.asarray(b) for _, b, _ in items]
+        fills = [np.asarray(f) for _, _, f in items]
+        for b, f in zip(boxes, fills):
+            if b.shape != (4,) or b.dtype != np.int64:
+                raise ValueError(f"erase box must be int64 [4], got {b.dtype} {b.shape}")
+            if f.dtype != np.uint8 or f.size != 3 * max(int(b[2]), 0) * max(int(b[3]), 0):
+                raise ValueError(f"erase fill must be uint8 [3, {b[2]}, {b[3]}], got {f.dtype} {f.shape}")
+        sizes = np.array([f.size for f in fills], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]) * (sizes > 0)
+        tab = np.concatenate([np.stack(boxes), offs[:, None]], axis=1)
+        erase = torch.from_numpy(check_erase(tab, int(sizes.sum()), size))
+        fill = torch.from_numpy(np.concatenate([f.reshape(-1) for f in fills]))
+    return mix, wdb, erase, fill
+
+
 def collate_packed(batch, repeats: int = 1, size: int = 224):
     """Device-augment collate: the repeat re-ordering of ``collate_and_shuffle``, then windows
     concatenated into one flat buffer with offsets written into the descriptors; op chains
-    (``DeviceTrainParams``) stacked into one validated [B, slots, AUG_P] table."""
+    (``DeviceTrainParams``) stacked into one validated [B, slots, AUG_P] table, AugMix mixing values
+    into a [B, W + 1] table and erase boxes into a [B, 5] table over one flat fill buffer."""
     batch = sum([batch[i::repeats] for i in range(repeats)], [])
     labels = None
-    if isinstance(batch[0][0], tuple):  # ((win, desc[, chain]), label)
+    if isinstance(batch[0][0], tuple):  # ((win, desc[, chain[, mix, box, fill]]), label)
         labels = torch.tensor([b[1] for b in batch])
         batch = [b[0] for b in batch]
     chain = None
-    if len(batch[0]) == 3:
+    extra = (None, None, None, None)
+    if len(batch[0]) >= 3:
         chain = torch.from_numpy(check_chain(np.stack([b[2] for b in batch])))
+        if len(batch[0]) == 6:
+            extra = _collate_mix_erase([b[3:] for b in batch], chain.shape[1], size)
         batch = [b[:2] for b in batch]
     tab = np.stack([d for _, d in batch])
     sizes = np.array([w.size for w, _ in batch], dtype=np.int64)
@@ -225,22 +316,38 @@ def collate_packed(batch, repeats: int = 1, size: int = 224):
     rows = tab[:, 1]
     tab[:, 12] = np.concatenate([[0], np.cumsum(rows * size * 3)[:-1]])
     src = torch.from_numpy(np.concatenate([w.reshape(-1) for w, _ in batch]))
-    packed = PackedImages(src, torch.from_numpy(tab), int((rows * size * 3).sum()), int(rows.max()), size, chain)
+    packed = PackedImages(src, torch.from_numpy(tab), int((rows * size * 3).sum()), int(rows.max()), size, chain,
+                          *extra)
     return packed if labels is None else (packed, labels)
 
 
 def unpack_on_device(p: PackedImages, device) -> torch.Tensor:
     """uint8 [B, 3, S, S] from a packed batch: H2D of the windows, then the resize / flip kernels
     (by the table's width: the random-resized-crop or the validation window resize) and, for a
-    batch with an op chain, the chain kernels -- all on the current stream."""
+    batch with an op chain, the chain kernels; for an AugMix batch the W chains on W replicas of
+    the resized batch, their composite, then the rest of the chain (ColorJitter); last the erase
+    boxes, in place -- all on the current stream."""
     from ..ops import _ext
     ext = _ext.load(True)
     src = p.src.to(device, non_blocking=True)
     tab = p.tab.to(device, non_blocking=True)
     resize = ext.window_resize if p.tab.shape[1] == WIN_TAB else ext.rrc_resize
     out = resize(src, tab, p.size, p.tmp_bytes, p.rows_max)
-    if p.chain is not None and p.chain.shape[1] > 0:
-        out = ext.aug_chain(out, p.chain.to(device, non_blocking=True), torch.empty_like(out))
+    chain = p.chain.to(device, non_blocking=True) if p.chain is not None and p.chain.shape[1] > 0 else None
+    if p.mix is not None:
+        W, D, blended = p.mix_wdb
+        B = out.shape[0]
+        rep = out.unsqueeze(1).repeat(1, W, 1, 1, 1).view(B * W, *out.shape[1:])  # always a copy: aug_chain consumes it
+        recs = chain[:, :W * D].reshape(B * W, D, chain.shape[2])
+        rep = ext.aug_chain(rep, recs, torch.empty_like(rep))
+        orig, out = out, ext.augmix_mix(out, rep, p.mix.to(device, non_blocking=True), bool(blended))
+        if chain.shape[1] > W * D:
+            out = ext.aug_chain(out, chain[:, W * D:].contiguous(), orig)  # the original is the free buffer now
+    elif chain is not None:
+        out = ext.aug_chain(out, chain, torch.empty_like(out))
+    if p.erase is not None and p.fill.numel() > 0:
+        out = ext.erase_paste(out, p.erase.to(device, non_blocking=True), p.fill.to(device, non_blocking=True),
+                              3 * int((p.erase[:, 2] * p.erase[:, 3]).max()))
     return out
 
 
@@ -258,6 +365,15 @@ def device_augment_ok(args) -> bool:
     aa = getattr(args, "auto_augment", "none") or "none"
     return (getattr(args, "random_crop", "rrc") == "rrc" and not getattr(args, "random_erasing", 0.0)
             and (aa == "none" or aa.startswith("rand") or aa.split("-")[0] in POLICIES))
+
+
+def device_augment_all_ok(args) -> bool:
+    """What ``--device-augment all`` covers: ``device_augment_ok`` plus AugMix (``augmix-*``) and
+    random erasing.  The ``src`` / ``none`` crops stay on the host."""
+    from .autoaugment import POLICIES
+    aa = getattr(args, "auto_augment", "none") or "none"
+    return (getattr(args, "random_crop", "rrc") == "rrc"
+            and (aa == "none" or aa.startswith("rand") or aa.startswith("augmix") or aa.split("-")[0] in POLICIES))
 
 
 def repeat_samples(samples, repeats: int = 1):
@@ -432,19 +548,20 @@ def create_dataloaders(args, rank: int = 0, world: int = 1, start_batches: int =
     """Returns (train_loader | None, valid_loader | None) like dataset.py:100-161.  ``start_batches``
     (resume): train batches already consumed on this rank -- the stream continues after them.
     ``device_augment``: train batches are ``PackedImages`` for ``unpack_on_device`` (requires
-    ``device_augment_ok(args)``).  ``device_valid``: validation batches are (``PackedImages``,
+    ``device_augment_all_ok(args)``; AugMix and random erasing ride along when the args ask for them).  ``device_valid``: validation batches are (``PackedImages``,
     labels) too (requires ``device_valid_ok(args)``); ``device_augment`` alone leaves them on PIL."""
     train_t, valid_t = create_transforms(args.random_crop, args.image_size, args.auto_augment, args.color_jitter,
                                          args.random_erasing, args.test_crop_ratio)
     if device_augment:
-        assert device_augment_ok(args), "device augment: AugMix, random erasing and src / none crops stay on the host"
+        assert device_augment_all_ok(args), "device augment: the src / none crops stay on the host"
         if device_augment_rrc_only(args):
             train_t = DeviceRRCParams(args.image_size)
         else:
-            from .transforms import ColorJitter, auto_augment_factory
-            cj = args.color_jitter
+            from .transforms import ColorJitter, RandomErasing, auto_augment_factory
+            cj, re = args.color_jitter, args.random_erasing
             train_t = DeviceTrainParams(args.image_size, auto_augment_factory(args.auto_augment or "none", args.image_size),
-                                        ColorJitter(cj, cj, cj) if cj > 0 else None)
+                                        ColorJitter(cj, cj, cj) if cj > 0 else None,
+                                        RandomErasing(re) if re > 0 else None)
     train_dl = valid_dl = None
     pin = torch.cuda.is_available()
     if getattr(args, "train_dataset_shards", None):

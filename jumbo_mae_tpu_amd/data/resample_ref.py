@@ -106,9 +106,19 @@ def unpack_packed(p) -> np.ndarray:
         n = int(d[1]) * int(d[2]) * 3
         outs.append(resize_window(src[int(d[0]):int(d[0]) + n], d, p.size))
     out = np.stack(outs)
-    if getattr(p, "chain", None) is not None:  # RandAugment / AutoAugment / ColorJitter records
+    chain = p.chain.numpy() if getattr(p, "chain", None) is not None else None
+    if getattr(p, "mix", None) is not None:  # AugMix: W chains of D records on replicas, composited; then the rest
+        from .augment_ref import apply_chain, augmix_mix
+        W, D, blended = p.mix_wdb
+        recs = np.ascontiguousarray(chain[:, :W * D]).reshape(len(out) * W, D, chain.shape[2])
+        out = augmix_mix(out, apply_chain(np.repeat(out, W, axis=0), recs), p.mix.numpy(), bool(blended))
+        out = apply_chain(out, chain[:, W * D:])
+    elif chain is not None:  # RandAugment / AutoAugment / ColorJitter records
         from .augment_ref import apply_chain
-        out = apply_chain(out, p.chain.numpy())
+        out = apply_chain(out, chain)
+    if getattr(p, "erase", None) is not None:  # RandomErasing boxes
+        from .augment_ref import erase_paste
+        out = erase_paste(out, p.erase.numpy(), p.fill.numpy())
     return out
 
 

@@ -191,6 +191,28 @@ class RandomErasing:
                 return a
         return a
 
+    def describe(self, size: int):
+        """The erase of a [3, size, size] image for the device augment (csrc/augment_chain.hip
+        erase_paste_kernel): __call__'s draws in its order -- the noise too, so the bytes are the
+        PIL path's -- and no image touched.  Returns (box int64 [i, j, eh, ew], fill uint8
+        [3, eh, ew]); an all-zero box and an empty fill when nothing is erased."""
+        none = np.zeros(4, np.int64), np.zeros((3, 0, 0), np.uint8)
+        if random.random() >= self.p:
+            return none
+        area = size * size
+        log_ratio = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        for _ in range(10):
+            ea = area * random.uniform(*self.scale)
+            ar = math.exp(random.uniform(*log_ratio))
+            eh = int(round(math.sqrt(ea * ar)))
+            ew = int(round(math.sqrt(ea / ar)))
+            if eh < size and ew < size:
+                i = random.randint(0, size - eh)
+                j = random.randint(0, size - ew)
+                fill = erase_fill(np.random.standard_normal((3, eh, ew)).astype(np.float32))
+                return (np.array([i, j, eh, ew], np.int64), fill) if fill.size else none
+        return none
+
 
 def auto_augment_factory(name: str, image_size: int):
     from .autoaugment import augmix_transform, auto_augment_transform, rand_augment_transform

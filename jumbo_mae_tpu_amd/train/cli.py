@@ -102,12 +102,14 @@ def _extensions(p: argparse.ArgumentParser):
                    help="end this invocation after N steps, writing 'last' (time-sliced / preemptible "
                         "jobs: continue with --resume auto); 0 = run to --training-steps")
     g.add_argument("--device", default=None, help="cuda|cpu (default: cuda if available)")
-    g.add_argument("--device-augment", default="auto", choices=["auto", "on", "off"],
+    g.add_argument("--device-augment", default="auto", choices=["auto", "on", "all", "off"],
                    help="train transform on the GPU, bit-exact to PIL: RandomResizedCrop + flip and, with 'on', "
                         "RandAugment (rand-*) / AutoAugment policies / --color-jitter after it (auto: on a GPU when the "
                         "train transform is RandomResizedCrop + flip only -- the pretraining presets; on: an error "
-                        "for AugMix, --random-erasing > 0 and --random-crop src|none, which stay on the host).  "
-                        "auto and on also run the validation transform (Resize + CenterCrop) on the GPU, bit-exact "
+                        "for AugMix, --random-erasing > 0 and --random-crop src|none, which stay on the host; all: "
+                        "what 'on' covers plus AugMix (augmix-*) and --random-erasing, i.e. the default finetune "
+                        "flags, and an error for --random-crop src|none only).  "
+                        "auto, on and all also run the validation transform (Resize + CenterCrop) on the GPU, bit-exact "
                         "to PIL, while int(image_size / test_crop_ratio) >= image_size; off keeps everything in "
                         "the loader workers")
     g.add_argument("--log-file-only", action="store_true", help="never use wandb even if installed")

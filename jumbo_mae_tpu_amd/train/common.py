@@ -57,27 +57,32 @@ def make_reducer(args, store):
 def use_device_augment(args, device) -> bool:
     """--device-augment: auto = on a GPU with the extension and the pretraining train transform
     (RandomResizedCrop + flip only); on = additionally RandAugment / AutoAugment / ColorJitter after
-    the crop (the finetune presets), and an error for what stays on the host."""
-    from ..data.loader import device_augment_ok, device_augment_rrc_only
+    the crop (the finetune presets), and an error for what stays on the host; all = additionally
+    AugMix and random erasing (the default finetune flags), and an error for --random-crop src|none."""
+    from ..data.loader import device_augment_all_ok, device_augment_ok, device_augment_rrc_only
     mode = getattr(args, "device_augment", "off")
     if mode == "off" or device.type != "cuda" or not getattr(args, "train_dataset_shards", None):
         return False
     if mode == "on" and not device_augment_ok(args):
         raise SystemExit("--device-augment on: AugMix (--auto-augment augmix-*), --random-erasing > 0 and "
                          "--random-crop src|none are not covered by the device augment; they run on the host "
-                         "(--device-augment off)")
-    if mode != "on" and not device_augment_rrc_only(args):
+                         "(--device-augment off; --device-augment all covers AugMix and random erasing)")
+    if mode == "all" and not device_augment_all_ok(args):
+        raise SystemExit("--device-augment all: --random-crop src|none are not covered by the device augment; "
+                         "they run on the host (--device-augment off)")
+    if mode not in ("on", "all") and not device_augment_rrc_only(args):
         return False
     from ..ops import _ext
     if not _ext.available():  # no built extension (JMAE_ALLOW_TORCH_FALLBACK runs): the PIL path
-        if mode == "on":
-            raise SystemExit("--device-augment on needs the built HIP extension (python -m jumbo_mae_tpu_amd.csrc.build)")
+        if mode in ("on", "all"):
+            raise SystemExit(f"--device-augment {mode} needs the built HIP extension "
+                             "(python -m jumbo_mae_tpu_amd.csrc.build)")
         return False
     return True
 
 
 def use_device_valid(args, device) -> bool:
-    """--device-augment auto | on also runs the validation transform (Resize -> CenterCrop) on the
+    """--device-augment auto | on | all also runs the validation transform (Resize -> CenterCrop) on the
     GPU -- bit-exact to PIL, so no metric changes: on a GPU with the extension, with validation
     shards, while the centre crop lies inside the resized image (``device_valid_ok``).  Raises for
     nothing: what it does not cover stays on the host."""

@@ -14,7 +14,9 @@ training rate.  Shards are written with real JPEG files at ImageNet-like sizes
 The augment flags override the mode's transform, so that the PIL and the device path can be
 measured per worker on one box with the same transform -- the config/ft.sh one is
 ``--mode finetune --auto-augment rand-m9-mstd0.5-inc1 --color-jitter 0 --random-erasing 0``
-(``--device-augment`` then runs RandAugment on the GPU too, csrc/augment_chain.hip).
+(``--device-augment`` then runs RandAugment on the GPU too, csrc/augment_chain.hip); with
+``--random-erasing P`` or ``--auto-augment augmix-*`` the device arm ships erase boxes with their fill
+bytes / AugMix chains as well (the line then reports ``fill_bytes_per_batch``, the extra H2D bytes).
 
 ``--valid``: the validation loader over the same shards (Resize(256, bicubic) + CenterCrop(224),
 padded final batch), PIL in the workers or -- with ``--device-augment`` -- decode-only workers and
@@ -104,7 +106,8 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--h2d", action="store_true", help="also through the DevicePrefetcher onto cuda:0")
     ap.add_argument("--device-augment", action="store_true",
-                    help="workers decode + ship crop windows; resize / flip on the GPU (csrc/augment.hip)")
+                    help="workers decode + ship crop windows; resize / flip on the GPU (csrc/augment.hip), with the "
+                         "op chains, AugMix and erase boxes of the transform (csrc/augment_chain.hip)")
     ap.add_argument("--auto-augment", default=None, help="train transform override (default: the mode's)")
     ap.add_argument("--color-jitter", type=float, default=None)
     ap.add_argument("--random-erasing", type=float, default=None)
@@ -135,9 +138,15 @@ def main():
         t0 = time.perf_counter()
         for _ in range(k):
             last = next(it)
+            p = last[0] if isinstance(last, (list, tuple)) else last
+            if getattr(p, "fill", None) is not None:  # erase fill bytes shipped with the packed batches
+                fill[0] += p.fill.numel()
+                fill[1] += 1
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         return k * batch / (time.perf_counter() - t0), last
+
+    fill = [0, 0]  # bytes, batches
 
     for nw in [int(x) for x in a.workers.split(",")]:
         largs = loader_args(spec, a.mode, a.batch, nw, **aug)
@@ -151,6 +160,9 @@ def main():
                "cpus": os.cpu_count()}
         if a.device_augment:
             out["window_kb_per_image"] = round(b.src.numel() / a.batch / 1024, 1)
+            if fill[1]:
+                out["fill_bytes_per_batch"] = round(fill[0] / fill[1])
+                fill[:] = [0, 0]
         del dl
         if a.h2d and torch.cuda.is_available():
             from jumbo_mae_tpu_amd.train.common import DevicePrefetcher

@@ -13,11 +13,14 @@ after ``--skip`` steps.  Then ``bench.py --batch-per-gpu B`` on the same box.
 
 ``--task finetune``: ``src/main_finetune.py`` with the config/ft.sh flags (ViT-B/16, RandAugment
 rand-m9-mstd0.5-inc1, mixup / cutmix) at 128 images per GPU (the per-GPU batch of the 8-GPU preset)
-against ``bench.py --task finetune`` at the same batch; ``--device-augment on|off`` selects the
+against ``bench.py --task finetune`` at the same batch; ``--device-augment on|all|off`` selects the
 device train transform (csrc/augment.hip + augment_chain.hip) or PIL in the workers.
+``--random-erasing P`` overrides the preset's 0.0 (0.25 is ``main_finetune``'s own default, which
+only ``all`` runs on the device).
 
     python tools/product_rate.py --out gpurun_out/prod [--steps 60] [--batch 512] [--workers 8]
-                                 [--task pretrain|finetune] [--device-augment on|off]
+                                 [--task pretrain|finetune] [--device-augment on|all|off]
+                                 [--random-erasing P]
     (under rocprofv3 --kernel-trace --memory-copy-trace: --driver-only, then tools/overlap_check.py)
 """
 
@@ -79,7 +82,7 @@ def ensure_shards(d, shards, per_shard, procs):
 def driver_cmd(a, spec, out_dir):
     ft = a.task == "finetune"
     return [sys.executable, "-u", os.path.join(ROOT, "src", "main_finetune.py" if ft else "main_pretrain.py"),
-            *(FT if ft else VITL),
+            *(FT if ft else VITL), *(["--random-erasing", str(a.random_erasing)] if a.random_erasing is not None else []),
             "--train-dataset-shards", spec, "--train-batch-size", str(a.batch), "--train-loader-workers",
             str(a.workers), "--device-augment", a.device_augment, "--training-steps", str(a.steps), "--warmup-steps", "5",
             "--log-interval", str(a.log_interval), "--eval-interval", "0", "--output-dir", out_dir,
@@ -115,7 +118,8 @@ def main():
     ap.add_argument("--skip", type=int, default=20, help="steps excluded from the steady state (warm-up, loader fill)")
     ap.add_argument("--log-interval", type=int, default=10)
     ap.add_argument("--task", default="pretrain", choices=["pretrain", "finetune"])
-    ap.add_argument("--device-augment", default="on", choices=["on", "off"])
+    ap.add_argument("--device-augment", default="on", choices=["on", "all", "off"])
+    ap.add_argument("--random-erasing", type=float, default=None, help="override the preset's --random-erasing")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: 512 pretrain, 128 finetune)")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--driver-only", action="store_true")
@@ -133,7 +137,8 @@ def main():
         return
     model = "ViT-B/16 finetune (config/ft.sh flags)" if a.task == "finetune" else "ViT-L/16 jumbo-MAE (preset flags)"
     res = {"config": {"model": model, "task": a.task, "per_gpu_batch": a.batch, "workers": a.workers,
-                      "steps": a.steps, "skip": a.skip, "device_augment": a.device_augment == "on",
+                      "steps": a.steps, "skip": a.skip, "device_augment": a.device_augment != "off",
+                      "device_augment_mode": a.device_augment, "random_erasing": a.random_erasing,
                       "cpus": os.cpu_count(),
                       "shards": f"{a.shards} x {a.per_shard} JPEG"}}
     res["driver"] = driver(a, spec, run_dir, os.path.join(a.out, "driver.log"))
