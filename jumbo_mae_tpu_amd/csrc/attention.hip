@@ -574,7 +574,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const uint16_t* __res
     const int r = i / NCH, c = (i % NCH) * 8;
     if (i < SP * NCH) {
       const int off = swo<NCH>(r, c);
-      *reinterpret_cast<uint4*>(Qs + off) = scale_bf16x8(qv[it], sl2);  // P = exp2(S) (see attn_bwd3_kernel)
+      *reinterpret_cast<uint4*>(Qs + off) = qv[it];  // unscaled: the fp32 score is scaled (see attn_bwd3_kernel)
       *reinterpret_cast<uint4*>(Ks + off) = kv[it];
       *reinterpret_cast<uint4*>(dOs + off) = dv[it];
     }
@@ -623,14 +623,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const uint16_t* __res
             const int q0 = qbase + 16 * half;
             const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + 4 * g);
             const float4 d4 = *reinterpret_cast<const float4*>(delta_s + q0 + 4 * g);
-            f32x4_t sacc = {l4.x + kneg, l4.y + kneg, l4.z + kneg, l4.w + kneg};
+            const f32x4_t nl = {l4.x, l4.y, l4.z, l4.w};  // -lse (log2 domain)
+            f32x4_t sacc = {kneg, kneg, kneg, kneg};
             f32x4_t dp = DROP ? f32x4_t{0.f, 0.f, 0.f, 0.f} : f32x4_t{d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
               sacc = mfma(ld8(Qs + q0 * HD + o_frag[kk]), kf[w][kk], sacc);
               dp = mfma(ld8(dOs + q0 * HD + o_frag[kk]), vf[w][kk], dp);
             }
-            // sacc[i] = S[q = q0 + 4g + i][key] (log2 domain, minus lse)
+            // sacc[i] = raw S[q = q0 + 4g + i][key]
             const float nd[4] = {d4.x, d4.y, d4.z, d4.w};  // -delta
             uint32_t dh[2] = {0u, 0u};  // one hash per query pair (q0 + 4g even)
             if constexpr (DROP) {
@@ -639,9 +640,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const uint16_t* __res
               dh[0] = drop_hash(jk, dseed);
               dh[1] = drop_hash(jk + 1, dseed);
             }
+            const f32x4_t ex = sacc * sl2 + nl;  // packed fp32: two v_pk_fma_f32 per four scores
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              const float p = __builtin_amdgcn_exp2f(sacc[i]);
+              const float p = __builtin_amdgcn_exp2f(ex[i]);
               if constexpr (DROP) {  // dS = P (M dP' / keep - delta); P^T dO uses M P (1 / keep at the end)
                 const bool kp = drop_keep_half(dh[i >> 1], i & 1, drop.thr);
                 pf[4 * half + i] = kp ? p : 0.f;
@@ -722,8 +724,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const uint16_t* __res
     if (kt < NT && key < S) {
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        float kv[4] = {dkacc[w][dt][0] * LN2, dkacc[w][dt][1] * LN2, dkacc[w][dt][2] * LN2,
-                       dkacc[w][dt][3] * LN2};  // Q staged times scale * log2(e)
+        float kv[4] = {dkacc[w][dt][0] * scale, dkacc[w][dt][1] * scale, dkacc[w][dt][2] * scale,
+                       dkacc[w][dt][3] * scale};
         const float vs = DROP ? drop.scale : 1.f;
         float vv[4] = {dvacc[w][dt][0] * vs, dvacc[w][dt][1] * vs, dvacc[w][dt][2] * vs, dvacc[w][dt][3] * vs};
         store4(dKg + (long)key * ts + dt * 16 + 4 * g, kv);
@@ -754,7 +756,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const uint16_t* __res
           float* bw = bsum + wave * 3 * HD;
           const int d = dt * 16 + 4 * g + i;
           bw[d] = sq * scale;
-          bw[HD + d] = sk * LN2;
+          bw[HD + d] = sk * scale;
           bw[2 * HD + d] = DROP ? sv * drop.scale : sv;
         }
       }
@@ -778,11 +780,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const uint16_t* __res
 //    tile (NKW = 4 key tiles per wave at S = 199);
 //  * per key tile issues the 8 independent S / dP MFMAs back to back, then the softmax-gradient
 //    VALU of all four 16-query slices, then the 8 dV / dK MFMAs;
-//  * runs the softmax gradient on two VALU instructions per score besides the bf16 packs: Q is
-//    staged pre-multiplied by scale * log2(e) and the S accumulator starts at -lse (log2
-//    domain), so P = exp2(S) with no per-score fma; the dP accumulator starts at -delta, so
-//    dS = P * dP with no per-score subtraction (dK then scales by ln 2 instead of the softmax
-//    scale).  Padded keys (only in the last key tile) add -1e30 to that init.
+//  * runs the softmax gradient on three VALU instructions per score besides the bf16 packs:
+//    P = exp2(fma(S, scale * log2(e), -lse)) on the raw fp32 score, as the forward does (Q staged
+//    pre-multiplied in bf16 saved the fma, but put a relative 2^-8 rounding on the logits that the
+//    forward does not have: at logits of hundreds of nats P came out several times too large,
+//    tests/test_attention_structured_gpu.py); the dP accumulator starts at -delta, so dS = P * dP
+//    with no per-score subtraction.  Padded keys (only in the last key tile) start the S
+//    accumulator at -1e30.
 // NWV waves per workgroup: 4 (the default), or 8 for hd 64 at long S, where the 4-wave form needs
 // more than 256 VGPRs (one wave per SIMD): 8 waves own half the key tiles each (half the dK / dV
 // accumulators) and sweep 128-query chunks (one 16-query dQ tile per wave), two waves per SIMD.
@@ -875,7 +879,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
     const int r = i / NCH, c = (i % NCH) * 8;
     if (i < SP * NCH) {
       const int off = swo<NCH>(r, c);
-      *reinterpret_cast<uint4*>(Qs + off) = scale_bf16x8(qv[it], sl2);
+      *reinterpret_cast<uint4*>(Qs + off) = qv[it];
       *reinterpret_cast<uint4*>(Ks + off) = kv[it];
       // dropout: dO staged times 1 / keep, so dP and P^T dO come out scaled (delta below is taken
       // from the unscaled dO)
@@ -943,7 +947,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
         // ---- key-tile independent fragments of this 32-query block
         const int qb = q0 + 32 * r;
         bf16x8_t qf[2][KK], dof[2][KK], a_do[DT], a_q[DT];
-        f32x4_t lv[2], dl[2];  // accumulator inits: -lse (log2 domain) and -delta
+        f32x4_t lv[2], dl[2];  // -lse (log2 domain) and the dP accumulator init -delta
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           if constexpr (!(DROP && NWV == 8)) {
@@ -970,21 +974,22 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
         };
         if constexpr (!TILE_AOP) load_aop();
         // one key tile: S / dP products from the accumulator inits, softmax gradient, dV / dK
-        // TILE_AOP: -lse / -delta re-read from LDS per tile too (kn: the padded-key init), so no
-        // per-block vectors stay live across the key tiles
-        auto tile = [&](int w, int kt, const f32x4_t (&ini)[2], float kn) {
-          f32x4_t sacc[2], dp[2], dlt[2];
+        // kn: the S accumulator init, 0 or -1e30 on padded keys.  TILE_AOP: -lse / -delta re-read
+        // from LDS per tile too, so no per-block vectors stay live across the key tiles
+        auto tile = [&](int w, int kt, float kn) {
+          f32x4_t sacc[2], dp[2], dlt[2], nl[2];
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) {
             if constexpr (TILE_AOP) {
               const float4 l4 = *reinterpret_cast<const float4*>(lse_s + qb + 16 * hh + 4 * g);
               const float4 d4 = *reinterpret_cast<const float4*>(delta_s + qb + 16 * hh + 4 * g);
-              sacc[hh] = f32x4_t{l4.x + kn, l4.y + kn, l4.z + kn, l4.w + kn};
+              nl[hh] = f32x4_t{l4.x, l4.y, l4.z, l4.w};
               dlt[hh] = f32x4_t{d4.x, d4.y, d4.z, d4.w};
             } else {
-              sacc[hh] = ini[hh];
+              nl[hh] = lv[hh];
               dlt[hh] = dl[hh];
             }
+            sacc[hh] = f32x4_t{kn, kn, kn, kn};
             dp[hh] = dlt[hh];
             if constexpr (TILE_AOP) {  // the Q / dO fragments too: nothing per block stays live
 #pragma unroll
@@ -1010,17 +1015,27 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
               dh[0] = drop_hash(jk, dseed);
               dh[1] = drop_hash(jk + 1, dseed);
             }
+            // whole-vector forms: two packed fp32 instructions per four scores (v_pk_fma_f32,
+            // v_pk_mul_f32) instead of four scalar ones
+            const f32x4_t ex = sacc[hh] * sl2 + nl[hh];
+            if constexpr (!DROP) {
+              const f32x4_t pv = {__builtin_amdgcn_exp2f(ex[0]), __builtin_amdgcn_exp2f(ex[1]),
+                                  __builtin_amdgcn_exp2f(ex[2]), __builtin_amdgcn_exp2f(ex[3])};
+              const f32x4_t dsv = pv * dp[hh];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float p = __builtin_amdgcn_exp2f(sacc[hh][i]);
+              for (int i = 0; i < 4; ++i) {
+                pf[4 * hh + i] = pv[i];
+                df[4 * hh + i] = dsv[i];
+              }
+            }
+#pragma unroll
+            for (int i = 0; i < (DROP ? 4 : 0); ++i) {
+              const float p = __builtin_amdgcn_exp2f(ex[i]);
               if constexpr (DROP) {  // dS = P (M dP' / keep - delta), dp = dP' / keep - delta (dO
                                      // staged scaled, -delta init); P^T dO uses M P
                 const bool kp = drop_keep_half(dh[i >> 1], i & 1, drop.thr);
                 pf[4 * hh + i] = kp ? p : 0.f;
                 df[4 * hh + i] = p * (kp ? dp[hh][i] : dlt[hh][i]);
-              } else {
-                pf[4 * hh + i] = p;
-                df[4 * hh + i] = p * dp[hh][i];
               }
             }
             uint2 pk;
@@ -1043,18 +1058,13 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
           if (NWV == 4 && NW * 16 * (w + 1) <= SMIN) {  // compile-time after the unroll (8 waves: spills)
             // full for every S of this instantiation: no branch around it, so the scheduler
             // interleaves these tiles' MFMA -> exp -> MFMA chains
-            tile(w, kt, lv, 0.f);
+            tile(w, kt, 0.f);
           } else if (kt * 16 + 16 <= S) {
-            tile(w, kt, lv, 0.f);
+            tile(w, kt, 0.f);
           } else if (kt * 16 < S) {  // the tile holding padded keys (wave-uniform branch); tiles
                                      // past S are skipped (their dS^T rows stay zero)
             asm volatile("" ::: "memory");  // keeps the two paths apart: no per-tile selects
-            if constexpr (TILE_AOP) {
-              tile(w, kt, lv, kneg[w]);
-            } else {
-              const f32x4_t lm[2] = {lv[0] + kneg[w], lv[1] + kneg[w]};
-              tile(w, kt, lm, 0.f);
-            }
+            tile(w, kt, kneg[w]);
           }
         }
       }
@@ -1105,8 +1115,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
     if (kt < NT && key < S) {
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        float kv2[4] = {dkacc[w][dt][0] * LN2, dkacc[w][dt][1] * LN2, dkacc[w][dt][2] * LN2,
-                        dkacc[w][dt][3] * LN2};
+        float kv2[4] = {dkacc[w][dt][0] * scale, dkacc[w][dt][1] * scale, dkacc[w][dt][2] * scale,
+                        dkacc[w][dt][3] * scale};
         float vv[4] = {dvacc[w][dt][0], dvacc[w][dt][1], dvacc[w][dt][2], dvacc[w][dt][3]};  // dO staged scaled
         store4(dKg + (long)key * ts + dt * 16 + 4 * g, kv2);
         store4(dVg + (long)key * ts + dt * 16 + 4 * g, vv);
@@ -1129,7 +1139,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
         if (l16 == 0) {
           float* bw = bsum + wave * 3 * HD;
           const int d = dt * 16 + 4 * g + i;
-          bw[HD + d] = sk * LN2;
+          bw[HD + d] = sk * scale;
           bw[2 * HD + d] = sv;
         }
       }

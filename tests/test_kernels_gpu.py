@@ -122,7 +122,7 @@ def _attn_ref(qkv, H):
                                       (2, 17, 4, 32), (5, 64, 3, 32), (2, 100, 3, 64), (2, 199, 4, 64),
                                       (3, 224, 2, 64), (2, 128, 2, 32), (1, 33, 5, 64), (32, 19, 4, 64),
                                       (11, 30, 2, 64), (2, 197, 16, 32), (2, 208, 2, 32), (2, 209, 2, 32),
-                                      (3, 72, 2, 32)])
+                                      (3, 72, 2, 32), (2, 80, 3, 64), (2, 160, 3, 64), (2, 160, 3, 32)])
 def test_attention(ext, B, S, H, hd):
     torch.manual_seed(0)
     D = H * hd
@@ -151,7 +151,8 @@ def test_attention(ext, B, S, H, hd):
 
 
 @pytest.mark.parametrize("B,S,H,hd", [(3, 52, 4, 64), (2, 199, 4, 32), (2, 199, 3, 64), (5, 17, 2, 32),
-                                      (9, 30, 2, 64), (2, 100, 2, 32), (3, 72, 2, 32)])
+                                      (9, 30, 2, 64), (2, 100, 2, 32), (3, 72, 2, 32), (2, 80, 2, 64),
+                                      (2, 160, 2, 64), (2, 160, 2, 32), (3, 52, 2, 32)])
 def test_attention_dropout(ext, B, S, H, hd):
     """Dropout on the attention probabilities inside the fused kernels (forward: masked P.V with
     the undropped row statistics; backward: the mask regenerated from the seed) against an fp64
@@ -303,7 +304,8 @@ def test_gemm_tile_rows_choice(ext):
     assert ext.gemm_nt_tiles(26624, 3072, 1024, 0, 1024) == 104 * 12
 
 
-@pytest.mark.parametrize("B,S,H,hd", [(2, 300, 4, 64), (1, 787, 3, 64), (2, 225, 2, 32), (1, 787, 2, 32)])
+@pytest.mark.parametrize("B,S,H,hd", [(2, 300, 4, 64), (1, 787, 3, 64), (2, 225, 2, 32), (1, 787, 2, 32),
+                                      (1, 321, 2, 64)])
 def test_attention_long_sequence_path(ext, B, S, H, hd):
     """S > attn_max_seq() (finetune at 448 px: S = 787) runs the tile-streamed online-softmax
     kernels (attn_fwd_long / attn_bwd_dq / attn_bwd_dkv); fp64 reference incl. gradients, through
