@@ -1161,6 +1161,75 @@ std::vector<torch::Tensor> residual_ln_fwd(torch::Tensor x, torch::Tensor y, c10
   return {x1, h, mean, rstd};
 }
 
+// ------------------------------------------------------------------------------ classification loss
+// Shared argument checks of cls_loss_fwd / cls_loss_bwd; returns (perm, w) device pointers or nulls
+static std::pair<const int*, const float*> check_cls_loss(const torch::Tensor& logits, const torch::Tensor& labels,
+                                                          const c10::optional<torch::Tensor>& perm,
+                                                          const c10::optional<torch::Tensor>& w, double smoothing,
+                                                          int64_t mode) {
+  CHECK_CUDA(logits);
+  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16 || logits.scalar_type() == torch::kFloat32,
+              "cls_loss: logits must be bf16 or fp32");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "cls_loss: logits must be [B, L]");
+  TORCH_CHECK(logits.stride(1) == 1, "cls_loss: logits must have a unit column stride");
+  TORCH_CHECK(logits.size(0) == 1 || logits.stride(0) >= logits.size(1), "cls_loss: logits rows must not overlap");
+  TORCH_CHECK(logits.size(0) < INT_MAX && logits.size(1) < INT_MAX, "cls_loss: logits too large");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(labels.device() == logits.device() && labels.scalar_type() == torch::kInt64 && labels.dim() == 1 &&
+                  labels.size(0) == B && labels.is_contiguous(),
+              "cls_loss: labels must be int64 [B] on the logits' device");
+  TORCH_CHECK(mode == 0 || mode == 1, "cls_loss: mode 0 (ce) or 1 (bce)");
+  TORCH_CHECK(smoothing >= 0.0 && smoothing < 1.0, "cls_loss: smoothing must be in [0, 1)");
+  const bool hp = perm.has_value() && perm->defined(), hw = w.has_value() && w->defined();
+  TORCH_CHECK(hp == hw, "cls_loss: perm and w come together");
+  if (!hp) return {nullptr, nullptr};
+  TORCH_CHECK(perm->device() == logits.device() && perm->scalar_type() == torch::kInt32 && perm->dim() == 1 &&
+                  perm->size(0) == B && perm->is_contiguous(),
+              "cls_loss: perm must be int32 [B] on the logits' device");
+  TORCH_CHECK(w->device() == logits.device() && w->scalar_type() == torch::kFloat32 && w->numel() == 1,
+              "cls_loss: w must be one fp32 element on the logits' device");
+  return {perm->data_ptr<int>(), w->data_ptr<float>()};
+}
+
+// a single row's stride is never used (and may be anything): the row length then
+static long row_stride(const torch::Tensor& logits) { return logits.size(0) == 1 ? logits.size(1) : logits.stride(0); }
+
+// [loss fp32 [B], hit bool [B, 2] (top-1, top-5), lse fp32 [B, 2] (hi, lo; zeros for bce)]
+std::vector<torch::Tensor> cls_loss_fwd(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tensor> perm,
+                                        c10::optional<torch::Tensor> w, double smoothing, int64_t mode) {
+  const auto pw = check_cls_loss(logits, labels, perm, w, smoothing, mode);
+  const int64_t B = logits.size(0);
+  auto loss = torch::empty({B}, logits.options().dtype(torch::kFloat32));
+  auto hit = torch::empty({B, 2}, logits.options().dtype(torch::kBool));
+  auto lse = torch::empty({B, 2}, logits.options().dtype(torch::kFloat32));
+  check_rc(jm_cls_loss_fwd(logits.data_ptr(), logits.scalar_type() == torch::kBFloat16, row_stride(logits),
+                           labels.data_ptr<int64_t>(), pw.first, pw.second, smoothing, (int)mode, (int)B,
+                           (int)logits.size(1), loss.data_ptr<float>(), reinterpret_cast<uint8_t*>(hit.data_ptr()),
+                           lse.data_ptr<float>(), stream()),
+           "cls_loss_fwd");
+  return {loss, hit, lse};
+}
+
+// dlogits [B, L] contiguous, in the dtype of logits
+torch::Tensor cls_loss_bwd(torch::Tensor dloss, torch::Tensor logits, torch::Tensor labels,
+                           c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> w, double smoothing,
+                           int64_t mode, torch::Tensor lse) {
+  const auto pw = check_cls_loss(logits, labels, perm, w, smoothing, mode);
+  const int64_t B = logits.size(0), L = logits.size(1);
+  TORCH_CHECK(lse.device() == logits.device() && lse.scalar_type() == torch::kFloat32 && lse.dim() == 2 &&
+                  lse.size(0) == B && lse.size(1) == 2 && lse.is_contiguous(),
+              "cls_loss_bwd: lse must be the forward's fp32 [B, 2]");
+  TORCH_CHECK(dloss.device() == logits.device() && dloss.scalar_type() == torch::kFloat32 && dloss.dim() == 1 &&
+                  dloss.size(0) == B && dloss.is_contiguous(),
+              "cls_loss_bwd: dloss must be fp32 [B] on the logits' device");
+  auto dlogits = torch::empty({B, L}, logits.options());
+  check_rc(jm_cls_loss_bwd(logits.data_ptr(), logits.scalar_type() == torch::kBFloat16, row_stride(logits),
+                           labels.data_ptr<int64_t>(), pw.first, pw.second, smoothing, (int)mode, (int)B, (int)L,
+                           lse.data_ptr<float>(), dloss.data_ptr<float>(), dlogits.data_ptr(), L, stream()),
+           "cls_loss_bwd");
+  return dlogits;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1168,8 +1237,8 @@ py::dict debug_lines() {
       {"augment", jm_debug_line_augment},     {"augment_chain", jm_debug_line_augment_chain},
       {"elementwise", jm_debug_line_elementwise},
       {"gemm", jm_debug_line_gemm},           {"gemm_tn", jm_debug_line_gemm_tn},
-      {"layernorm", jm_debug_line_layernorm}, {"mae", jm_debug_line_mae},
-      {"optim", jm_debug_line_optim}};
+      {"layernorm", jm_debug_line_layernorm}, {"loss", jm_debug_line_loss},
+      {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1273,6 +1342,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("patch_mse_fwd", &patch_mse_fwd);
   m.def("mix_patches", &mix_patches);
   m.def("patch_mse_bwd", &patch_mse_bwd);
+  m.def("cls_loss_fwd", &cls_loss_fwd, py::arg("logits"), py::arg("labels"), py::arg("perm") = py::none(),
+        py::arg("w") = py::none(), py::arg("smoothing") = 0.0, py::arg("mode") = 0);
+  m.def("cls_loss_bwd", &cls_loss_bwd, py::arg("dloss"), py::arg("logits"), py::arg("labels"),
+        py::arg("perm"), py::arg("w"), py::arg("smoothing"), py::arg("mode"), py::arg("lse"));
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

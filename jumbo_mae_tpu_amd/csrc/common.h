@@ -151,8 +151,9 @@ constexpr int GD_Z = 34;
 // v_cvt_pk_u8_f32 rounds to nearest even and saturates to [0, 255] (probed on gfx950:
 // tools/probes/cvt_pk_u8_probe.hip) and writes its byte into a word: one instruction per code
 // instead of the clamp / truncating convert / shift / or sequence -- the FF1 forward epilogue is
-// VALU-issue bound (profiles/r6h_gelu_code_cvt.txt).  Ties round to even (the torch mirror
-// gd_encode rounds them up: codes may differ by one at exact ties).
+// VALU-issue bound (profiles/r6h_gelu_code_cvt.txt).  Ties round to even, as in the torch mirror
+// gd_encode (torch.round); what remains is the fma's single rounding against the mirror's separate
+// multiply and add, so codes may differ by one where GD_Q d + GD_Z lands next to a tie.
 JM_DEVICE uint32_t gd_code(float d) { return __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(d, GD_Q, (float)GD_Z), 0, 0u); }
 template <int B>
 JM_DEVICE uint32_t gd_put(float d, uint32_t w) { return __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(d, GD_Q, (float)GD_Z), B, w); }

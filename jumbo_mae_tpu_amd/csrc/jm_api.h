@@ -303,3 +303,14 @@ int jm_augmix_mix(const uint8_t* orig, const uint8_t* chains, const float* table
 int jm_erase_paste(uint8_t* images, const int64_t* table, const uint8_t* fill, long fill_len, int B, int S,
                    long box_bytes_max, hipStream_t st);
 int jm_debug_line_augment_chain();
+
+// ---- loss.hip (logits: bf16 or fp32 [B, L] rows ld elements apart; labels int64 [B]; perm int32 [B] and
+// w, the device label weight, both or neither; smoothing in [0, 1); mode 0 = softmax CE, 1 = sigmoid BCE; -1 bad argument, -2 failed launch)
+// loss fp32 [B], hit bytes [B, 2] (top-1, top-5 membership of the arg-max label set), lse fp32 [B, 2] (hi, lo)
+int jm_cls_loss_fwd(const void* logits, int bf16, long ld, const int64_t* labels, const int* perm, const float* w,
+                    double smoothing, int mode, int B, int L, float* loss, uint8_t* hit, float* lse, hipStream_t st);
+// dlogits [B, L] (rows ldo apart, the dtype of logits) = dloss[b] times the gradient of row b's loss
+int jm_cls_loss_bwd(const void* logits, int bf16, long ld, const int64_t* labels, const int* perm, const float* w,
+                    double smoothing, int mode, int B, int L, const float* lse, const float* dloss, void* dlogits,
+                    long ldo, hipStream_t st);
+int jm_debug_line_loss();

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from ..config import ViTConfig
 from ..ops import functional as Fn
 from ..ops import mae as mae_ops
+from ..ops import prims as P
 from ..utils.mixup import Mixup, smooth_labels
 from .params import ParamStore
 from .vit import JumboViT, LinearCLS
@@ -37,6 +38,9 @@ def sigmoid_bce(logits, labels):
 
 
 CRITERION_COLLECTION = {"ce": softmax_cross_entropy, "bce": sigmoid_bce}
+
+
+_DRAW = object()  # patches / logits: take the batch's plan from step_plan
 
 
 def _capturing() -> bool:
@@ -56,6 +60,7 @@ class FinetuneModel:
         self.mixup = mixup or Mixup(0.0, 0.0)
         self.label_smoothing = label_smoothing if criterion == "ce" else 0.0
         self.criterion = CRITERION_COLLECTION[criterion]
+        self.criterion_name = criterion
         self.group = group
 
     def to(self, device, compute_dtype=torch.float32, seed: int = 0):
@@ -81,16 +86,24 @@ class FinetuneModel:
         B, _, H, W = images_u8.shape
         self._plans[i] = self.mixup.plan(B, H, W, images_u8.device, tag=str(i))
 
-    def patches(self, images_u8, labels, rngs, det):
-        """(patch rows [B*N, p*p*3] in the compute dtype, labels) -- Mixup / CutMix applied when
-        training (one plan per batch; the blend is fused into the patch gather on the GPU)."""
+    def step_plan(self, images_u8, rngs, det):
+        """This batch's Mixup / CutMix plan (None when not training or mixing is off): the one
+        ``prepare_step`` drew for the current micro-batch, or a fresh draw for a direct call."""
+        if det or not self.mixup.active:
+            return None
         B, _, H, W = images_u8.shape
-        plan = None
-        if not det and self.mixup.active:
-            plans = getattr(self, "_plans", {})
-            plan = plans.pop(self.micro_index, None) if not _capturing() else plans.get(self.micro_index)
-            if plan is None:  # direct forward call without a prepared step: draw here
-                plan = self.mixup.plan(B, H, W, images_u8.device, rngs.get("mixup") if rngs else None)
+        plans = getattr(self, "_plans", {})
+        plan = plans.pop(self.micro_index, None) if not _capturing() else plans.get(self.micro_index)
+        if plan is None:  # direct forward call without a prepared step: draw here
+            plan = self.mixup.plan(B, H, W, images_u8.device, rngs.get("mixup") if rngs else None)
+        return plan
+
+    def patches(self, images_u8, labels, rngs, det, plan=_DRAW):
+        """(patch rows [B*N, p*p*3] in the compute dtype, labels) -- Mixup / CutMix applied when
+        training (one plan per batch, ``step_plan`` unless the caller passes the plan it took; the
+        blend is fused into the patch gather on the GPU)."""
+        if plan is _DRAW:
+            plan = self.step_plan(images_u8, rngs, det)
         if labels is not None:
             labels = Mixup.mix_labels(labels, plan)
         rows = mae_ops.mixed_patches(images_u8, plan, self.cfg.patch_size, self.store.compute_dtype)
@@ -105,18 +118,33 @@ class FinetuneModel:
         h = Fn.layer_norm(x[:, :C], self.encoder.norm.g, self.encoder.norm.b, torch.float32)
         return h.reshape(B, C * cfg.dim)
 
-    def logits(self, images_u8, labels=None, rngs=None, det=True):
+    def logits(self, images_u8, labels=None, rngs=None, det=True, raw=False, plan=_DRAW):
+        """(logits, mixed labels); ``raw``: the head's output in the compute dtype instead of fp32;
+        ``plan``: as in ``patches``."""
         B = images_u8.shape[0]
-        rows, labels = self.patches(images_u8, labels, rngs, det)
+        rows, labels = self.patches(images_u8, labels, rngs, det, plan)
         if self.cfg.linear_probing:
             with torch.no_grad():
                 feats = self.features(rows, B, rngs, det)
         else:
             feats = self.features(rows, B, rngs, det)
-        return self.head(feats, det, self.group), labels
+        return self.head(feats, det, self.group, raw), labels
 
     # ---------------------------------------------------------------- train / eval
+    def _fused_loss(self, images_u8, labels) -> bool:
+        """Integer class ids on the GPU: loss and accuracies come from ``Fn.cls_loss`` on the head's own
+        (bf16) logits and the plan's device buffers; no dense target is built.  Dense soft labels and
+        the CPU keep the torch composition below."""
+        return (labels.dim() == 1 and not labels.is_floating_point() and labels.is_cuda and P._CLS_LOSS_OURS
+                and P.hip(images_u8))
+
     def forward(self, images_u8, labels, rngs=None, det=False):
+        if self._fused_loss(images_u8, labels):
+            plan = self.step_plan(images_u8, rngs, det)
+            logits, _ = self.logits(images_u8, None, rngs, det, raw=True, plan=plan)
+            loss, acc1, acc5 = Fn.cls_loss(logits, labels, plan, 0.0 if det else self.label_smoothing,
+                                           self.criterion_name)
+            return {"loss": loss.mean(), "acc1": acc1.float().mean(), "acc5": acc5.float().mean()}
         labels = self._prep_labels(labels)
         if not det:
             labels = smooth_labels(labels, self.label_smoothing)
@@ -145,6 +173,13 @@ class FinetuneModel:
     def evaluate(self, images_u8, labels, rngs=None) -> dict:
         """Sums over valid (label != -1) samples, like validation_step (finetuning.py:157-165)."""
         valid = (labels != -1)
+        if self._fused_loss(images_u8, labels):
+            logits, _ = self.logits(images_u8, None, rngs, det=True, raw=True)
+            loss, acc1, acc5 = Fn.cls_loss(logits, torch.where(valid, labels, torch.zeros_like(labels)), None, 0.0,
+                                           self.criterion_name)
+            v = valid.float()
+            return {"loss": (loss * v).sum(), "acc1": (acc1.float() * v).sum(), "acc5": (acc5.float() * v).sum(),
+                    "num_samples": v.sum()}
         lab = self._prep_labels(torch.where(valid, labels, torch.zeros_like(labels)))
         logits, _ = self.logits(images_u8, lab, rngs, det=True)
         loss = self.criterion(logits, lab)

@@ -494,10 +494,12 @@ class LinearCLS:
             self.running_mean = torch.zeros(self.dim, device=device)
             self.running_var = torch.ones(self.dim, device=device)
 
-    def __call__(self, x: torch.Tensor, det: bool, group=None) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, det: bool, group=None, raw: bool = False) -> torch.Tensor:
+        """fp32 logits; ``raw``: the Dense's own output in the compute dtype (no fp32 copy)."""
         if self.batch_norm:
             from ..parallel.syncbn import sync_batch_norm
             x = sync_batch_norm(x, self.bn_scale, self.bn_bias, self.running_mean, self.running_var,
                                 training=not det, momentum=0.99, eps=1e-5, group=group)
         dt = self.dense.k.store.compute_dtype
-        return self.dense(x.to(dt)).float()
+        y = self.dense(x.to(dt))
+        return y if raw else y.float()

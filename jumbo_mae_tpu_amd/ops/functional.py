@@ -160,3 +160,69 @@ class _Attention(torch.autograd.Function):
 
 def attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     return _Attention.apply(qkv, heads)
+
+
+# ---------------------------------------------------------------- classification loss + accuracy
+def cls_loss_torch(logits, labels_int, plan=None, smoothing: float = 0.0, criterion: str = "ce"):
+    """The torch composition of models/classifier.py on integer labels: scattered one-hot ->
+    ``smooth_labels`` -> ``Mixup.mix_labels`` -> criterion and top-1 / top-5 membership in the
+    arg-max label set.  The CPU path of ``cls_loss``, and what defines the kernels' semantics."""
+    from ..models.classifier import CRITERION_COLLECTION, FinetuneModel  # (imports this module)
+    from ..utils.mixup import Mixup, smooth_labels
+
+    B, L = logits.shape
+    idx = labels_int.long().clamp(0, L - 1).view(-1, 1)
+    t = torch.zeros(B, L, device=logits.device).scatter_(1, idx, 1.0)
+    t = Mixup.mix_labels(smooth_labels(t, smoothing), plan)
+    logits = logits.float()
+    acc1, acc5 = FinetuneModel.accuracy(logits, t)
+    return CRITERION_COLLECTION[criterion](logits, t), acc1, acc5
+
+
+class _ClsLoss(torch.autograd.Function):
+    """logits [B, L] (bf16 or fp32, unit column stride) -> per-row loss and the bool [B, 2] hits
+    (csrc/loss.hip); the dense targets exist only as (labels, perm, w)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, perm, w, smoothing: float, mode: int):
+        loss, hit, lse = P._ext.load().cls_loss_fwd(logits, labels, perm, w, smoothing, mode)
+        ctx.save_for_backward(logits, labels, perm, w, lse)
+        ctx.smoothing, ctx.mode = smoothing, mode
+        ctx.mark_non_differentiable(hit)
+        return loss, hit
+
+    @staticmethod
+    def backward(ctx, dloss, _dhit):
+        logits, labels, perm, w, lse = ctx.saved_tensors
+        dz = P._ext.load().cls_loss_bwd(dloss.float().contiguous(), logits, labels, perm, w, ctx.smoothing, ctx.mode,
+                                        lse)
+        return dz, None, None, None, None, None
+
+
+def _plan_buffers(plan, device):
+    """(perm int32 [B], w fp32 [1]) of a Mixup plan on the device: its static buffers when it has them."""
+    if plan is None:
+        return None, None
+    dev = plan.get("dev")
+    if dev is not None:
+        return dev["perm"], dev["params"][2:3]
+    perm = torch.as_tensor(plan["perm"]).to(device=device, dtype=torch.int32).contiguous()
+    return perm, torch.as_tensor(plan["label_w_t"], dtype=torch.float32).to(device).reshape(1)
+
+
+def cls_loss(logits: torch.Tensor, labels_int: torch.Tensor, plan: dict | None = None, smoothing: float = 0.0,
+             criterion: str = "ce"):
+    """(loss [B] fp32, acc1 [B] bool, acc5 [B] bool) of integer class ids against ``logits`` [B, L]:
+    ``criterion`` ("ce" | "bce") on the one-hot targets smoothed by ``smoothing`` and mixed per the
+    Mixup ``plan``.  On the GPU one fused kernel each way (the accuracies carry no gradient); on the
+    CPU, or with ``prims._CLS_LOSS_OURS`` off, the torch composition ``cls_loss_torch``."""
+    if not (P._CLS_LOSS_OURS and P.hip(logits)):
+        return cls_loss_torch(logits, labels_int, plan, smoothing, criterion)
+    if criterion not in ("ce", "bce"):
+        raise KeyError(criterion)
+    if logits.stride(-1) != 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        logits = logits.contiguous()  # strided columns or overlapping rows (an expanded batch)
+    perm, w = _plan_buffers(plan, logits.device)
+    loss, hit = _ClsLoss.apply(logits, labels_int.long().contiguous(), perm, w, float(smoothing),
+                               0 if criterion == "ce" else 1)
+    return loss, hit[:, 0], hit[:, 1]

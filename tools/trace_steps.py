@@ -26,6 +26,8 @@ def category(n: str) -> str:
         return "layernorm"
     if any(x in n for x in ("rowcol", "gelu", "residual", "splitk", "colsum", "transpose_bf16", "zero_")):
         return "fused elementwise (ours)"
+    if "cls_loss" in n:
+        return "classification loss (ours)"
     if "adamw" in n or "opt" in n.lower() or "sumsq" in n or "lamb" in n or "lars" in n or "chunk_sums" in n:
         return "optimizer"
     if "at::native" in n:
@@ -49,6 +51,7 @@ def main():
         raise SystemExit(f"fewer than two '{a.marker}' launches in the trace")
     pairs = list(zip(marks[:-1], marks[1:]))[-a.last:]
     cat = collections.Counter()
+    cn = collections.Counter()
     kt = collections.Counter()
     kn = collections.Counter()
     busy = wall = 0.0
@@ -60,12 +63,14 @@ def main():
             n = r["Kernel_Name"]
             busy += d
             cat[category(n)] += d
+            cn[category(n)] += 1
             kt[n] += d
             kn[n] += 1
     ns = len(pairs)
-    print(f"{ns} steady-state steps: wall {wall / ns:.2f} ms/step, kernel busy {busy / ns:.2f} ms/step")
+    print(f"{ns} steady-state steps: wall {wall / ns:.2f} ms/step, kernel busy {busy / ns:.2f} ms/step, "
+          f"{sum(cn.values()) / ns:.1f} launches/step")
     for k, v in cat.most_common():
-        print(f"  {k:28s} {v / ns:8.3f} ms/step")
+        print(f"  {k:28s} {v / ns:8.3f} ms/step  {cn[k] / ns:7.1f} launches/step")
     print()
     for n, v in kt.most_common(a.top):
         print(f"{v / ns:8.3f} ms  {kn[n] / ns:6.1f}/step  {n[:110]}")
