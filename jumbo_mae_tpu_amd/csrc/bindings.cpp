@@ -1230,10 +1230,190 @@ torch::Tensor cls_loss_bwd(torch::Tensor dloss, torch::Tensor logits, torch::Ten
   return dlogits;
 }
 
+// ------------------------------------------------------------------------------ batch norm
+// Argument checks of the bn_* entry points.  Dtypes, shapes and strides are checked before the
+// devices, and everything before any launch, so each message can be reached with CPU tensors.
+// A [B, J] operand `what` (x, dy, out): dtype (bf16 allowed or fp32 only), 2-D, unit column stride, rows apart
+static void check_bn_mat(const torch::Tensor& t, const char* fn, const char* what, bool bf16_ok) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 || (bf16_ok && t.scalar_type() == torch::kBFloat16), fn, ": ", what,
+              bf16_ok ? " must be bf16 or fp32" : " must be fp32");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1, fn, ": ", what, " must be [B, J]");
+  TORCH_CHECK(t.stride(1) == 1, fn, ": ", what, " must have a unit column stride");
+  TORCH_CHECK(t.size(0) == 1 || t.stride(0) >= t.size(1), fn, ": ", what, " rows must not overlap");
+  TORCH_CHECK(t.size(0) < INT_MAX && t.size(1) < INT_MAX, fn, ": ", what, " too large");
+}
+
+// a second [B, J] operand against x
+static void check_bn_like(const torch::Tensor& t, const torch::Tensor& x, const char* fn, const char* what,
+                          bool bf16_ok) {
+  check_bn_mat(t, fn, what, bf16_ok);
+  TORCH_CHECK(t.size(0) == x.size(0) && t.size(1) == x.size(1), fn, ": ", what, " must have the shape of x");
+}
+
+// a contiguous fp32 vector of n elements
+static void check_bn_vec(const torch::Tensor& t, int64_t n, const char* fn, const char* what, const char* shape) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.dim() == 1 && t.size(0) == n && t.is_contiguous(), fn, ": ",
+              what, " must be fp32 ", shape);
+}
+
+// last: one device, a GPU
+static void check_bn_device(const torch::Tensor& x, std::initializer_list<const torch::Tensor*> others,
+                            const char* fn) {
+  for (const torch::Tensor* t : others)
+    TORCH_CHECK(t->device() == x.device(), fn, ": all tensors must be on the device of x");
+  TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
+}
+
+static bool bn_out_bf16(py::object out_dtype, const char* fn) {
+  const auto odt = torch::python::detail::py_object_to_dtype(out_dtype);
+  TORCH_CHECK(odt == torch::kBFloat16 || odt == torch::kFloat32, fn, ": out_dtype must be bf16 or fp32");
+  return odt == torch::kBFloat16;
+}
+
+static torch::Tensor bn_part(const torch::Tensor& x) {
+  return torch::empty({(int64_t)jm_bn_chunks((int)x.size(0)), 2, x.size(1)}, x.options().dtype(torch::kFloat64));
+}
+
+// packed fp32 [2 J] = [mean, mean of squares] of the rows of x
+torch::Tensor bn_stats(torch::Tensor x) {
+  check_bn_mat(x, "bn_stats", "x", false);
+  check_bn_device(x, {}, "bn_stats");
+  const int64_t B = x.size(0), J = x.size(1);
+  auto part = bn_part(x);
+  auto packed = torch::empty({2 * J}, x.options());
+  check_rc(jm_bn_stats(x.data_ptr<float>(), row_stride(x), (int)B, (int)J, part.data_ptr<double>(),
+                       packed.data_ptr<float>(), stream()),
+           "bn_stats");
+  return packed;
+}
+
+// [y (out_dtype; written into out when given), stats fp32 [2, J] = (mean, rstd)]; the running statistics move in place
+std::vector<torch::Tensor> bn_apply(torch::Tensor x, torch::Tensor packed, torch::Tensor gamma, torch::Tensor beta,
+                                    torch::Tensor running_mean, torch::Tensor running_var, double eps, double momentum,
+                                    py::object out_dtype, c10::optional<torch::Tensor> out) {
+  const char* fn = "bn_apply";
+  check_bn_mat(x, fn, "x", false);
+  const int64_t B = x.size(0), J = x.size(1);
+  check_bn_vec(packed, 2 * J, fn, "packed", "[2 J]");
+  check_bn_vec(gamma, J, fn, "gamma", "[J]");
+  check_bn_vec(beta, J, fn, "beta", "[J]");
+  check_bn_vec(running_mean, J, fn, "running_mean", "[J]");
+  check_bn_vec(running_var, J, fn, "running_var", "[J]");
+  const bool bf16 = bn_out_bf16(out_dtype, fn);
+  TORCH_CHECK(eps > 0.0 && momentum >= 0.0 && momentum <= 1.0, fn, ": eps > 0 and momentum in [0, 1]");
+  const bool has_out = out.has_value() && out->defined();
+  if (has_out) {
+    check_bn_like(*out, x, fn, "out", true);
+    TORCH_CHECK((out->scalar_type() == torch::kBFloat16) == bf16, fn, ": out must have out_dtype");
+    check_bn_device(x, {&packed, &gamma, &beta, &running_mean, &running_var, &*out}, fn);
+  } else {
+    check_bn_device(x, {&packed, &gamma, &beta, &running_mean, &running_var}, fn);
+  }
+  auto y = has_out ? *out : torch::empty({B, J}, x.options().dtype(bf16 ? torch::kBFloat16 : torch::kFloat32));
+  auto stats = torch::empty({2, J}, x.options());
+  check_rc(jm_bn_apply(x.data_ptr<float>(), row_stride(x), (int)B, (int)J, packed.data_ptr<float>(),
+                       gamma.data_ptr<float>(), beta.data_ptr<float>(), eps, momentum, y.data_ptr(), bf16,
+                       row_stride(y), stats.data_ptr<float>(), running_mean.data_ptr<float>(),
+                       running_var.data_ptr<float>(), stream()),
+           fn);
+  return {y, stats};
+}
+
+// y from the running statistics (inference); nothing else is written
+torch::Tensor bn_apply_eval(torch::Tensor x, torch::Tensor running_mean, torch::Tensor running_var, torch::Tensor gamma,
+                            torch::Tensor beta, double eps, py::object out_dtype, c10::optional<torch::Tensor> out) {
+  const char* fn = "bn_apply_eval";
+  check_bn_mat(x, fn, "x", false);
+  const int64_t B = x.size(0), J = x.size(1);
+  check_bn_vec(running_mean, J, fn, "running_mean", "[J]");
+  check_bn_vec(running_var, J, fn, "running_var", "[J]");
+  check_bn_vec(gamma, J, fn, "gamma", "[J]");
+  check_bn_vec(beta, J, fn, "beta", "[J]");
+  const bool bf16 = bn_out_bf16(out_dtype, fn);
+  TORCH_CHECK(eps > 0.0, fn, ": eps > 0");
+  const bool has_out = out.has_value() && out->defined();
+  if (has_out) {
+    check_bn_like(*out, x, fn, "out", true);
+    TORCH_CHECK((out->scalar_type() == torch::kBFloat16) == bf16, fn, ": out must have out_dtype");
+    check_bn_device(x, {&running_mean, &running_var, &gamma, &beta, &*out}, fn);
+  } else {
+    check_bn_device(x, {&running_mean, &running_var, &gamma, &beta}, fn);
+  }
+  auto y = has_out ? *out : torch::empty({B, J}, x.options().dtype(bf16 ? torch::kBFloat16 : torch::kFloat32));
+  check_rc(jm_bn_apply_eval(x.data_ptr<float>(), row_stride(x), (int)B, (int)J, running_mean.data_ptr<float>(),
+                            running_var.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), eps,
+                            y.data_ptr(), bf16, row_stride(y), stream()),
+           fn);
+  return y;
+}
+
+// shared by the two backward entry points
+static void check_bn_bwd(const torch::Tensor& dy, const torch::Tensor& x, const torch::Tensor& stats,
+                         const torch::Tensor& gamma, const char* fn) {
+  check_bn_mat(x, fn, "x", false);
+  check_bn_like(dy, x, fn, "dy", true);
+  const int64_t J = x.size(1);
+  TORCH_CHECK(stats.scalar_type() == torch::kFloat32 && stats.dim() == 2 && stats.size(0) == 2 && stats.size(1) == J &&
+                  stats.is_contiguous(),
+              fn, ": stats must be the forward's fp32 [2, J]");
+  check_bn_vec(gamma, J, fn, "gamma", "[J]");
+}
+
+// [dgamma, dbeta, packed_g fp32 [2 J] = gamma (sum dy, sum dy xhat)]; dgamma / dbeta given: added to in place
+std::vector<torch::Tensor> bn_bwd_reduce(torch::Tensor dy, torch::Tensor x, torch::Tensor stats, torch::Tensor gamma,
+                                         c10::optional<torch::Tensor> dgamma, c10::optional<torch::Tensor> dbeta) {
+  const char* fn = "bn_bwd_reduce";
+  check_bn_bwd(dy, x, stats, gamma, fn);
+  const int64_t B = x.size(0), J = x.size(1);
+  const bool acc = dgamma.has_value() && dgamma->defined();
+  TORCH_CHECK(acc == (dbeta.has_value() && dbeta->defined()), fn, ": dgamma and dbeta come together");
+  if (acc) {
+    check_bn_vec(*dgamma, J, fn, "dgamma", "[J]");
+    check_bn_vec(*dbeta, J, fn, "dbeta", "[J]");
+    check_bn_device(x, {&dy, &stats, &gamma, &*dgamma, &*dbeta}, fn);
+  } else {
+    check_bn_device(x, {&dy, &stats, &gamma}, fn);
+  }
+  auto dg = acc ? *dgamma : torch::empty({J}, x.options());
+  auto db = acc ? *dbeta : torch::empty({J}, x.options());
+  auto part = bn_part(x);
+  auto packed_g = torch::empty({2 * J}, x.options());
+  check_rc(jm_bn_bwd_reduce(dy.data_ptr(), dy.scalar_type() == torch::kBFloat16, row_stride(dy), x.data_ptr<float>(),
+                            row_stride(x), (int)B, (int)J, stats.data_ptr<float>(), gamma.data_ptr<float>(),
+                            part.data_ptr<double>(), dg.data_ptr<float>(), db.data_ptr<float>(), acc,
+                            packed_g.data_ptr<float>(), stream()),
+           fn);
+  return {dg, db, packed_g};
+}
+
+// dx fp32 [B, J] (written into out when given); n = rows of the global batch
+torch::Tensor bn_bwd_dx(torch::Tensor dy, torch::Tensor x, torch::Tensor stats, torch::Tensor gamma,
+                        torch::Tensor packed_g, double n, c10::optional<torch::Tensor> out) {
+  const char* fn = "bn_bwd_dx";
+  check_bn_bwd(dy, x, stats, gamma, fn);
+  const int64_t B = x.size(0), J = x.size(1);
+  check_bn_vec(packed_g, 2 * J, fn, "packed_g", "[2 J]");
+  TORCH_CHECK(n >= (double)B, fn, ": n counts at least the local rows");
+  const bool has_out = out.has_value() && out->defined();
+  if (has_out) {
+    check_bn_like(*out, x, fn, "out", false);
+    check_bn_device(x, {&dy, &stats, &gamma, &packed_g, &*out}, fn);
+  } else {
+    check_bn_device(x, {&dy, &stats, &gamma, &packed_g}, fn);
+  }
+  auto dx = has_out ? *out : torch::empty({B, J}, x.options());
+  check_rc(jm_bn_bwd_dx(dy.data_ptr(), dy.scalar_type() == torch::kBFloat16, row_stride(dy), x.data_ptr<float>(),
+                        row_stride(x), (int)B, (int)J, stats.data_ptr<float>(), gamma.data_ptr<float>(),
+                        packed_g.data_ptr<float>(), n, dx.data_ptr<float>(), row_stride(dx), stream()),
+           fn);
+  return dx;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
       {"attention", jm_debug_line_attention}, {"dropout", jm_debug_line_dropout},
+      {"batchnorm", jm_debug_line_batchnorm},
       {"augment", jm_debug_line_augment},     {"augment_chain", jm_debug_line_augment_chain},
       {"elementwise", jm_debug_line_elementwise},
       {"gemm", jm_debug_line_gemm},           {"gemm_tn", jm_debug_line_gemm_tn},
@@ -1346,6 +1526,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w") = py::none(), py::arg("smoothing") = 0.0, py::arg("mode") = 0);
   m.def("cls_loss_bwd", &cls_loss_bwd, py::arg("dloss"), py::arg("logits"), py::arg("labels"),
         py::arg("perm"), py::arg("w"), py::arg("smoothing"), py::arg("mode"), py::arg("lse"));
+  m.def("bn_stats", &bn_stats, py::arg("x"));
+  m.def("bn_apply", &bn_apply, py::arg("x"), py::arg("packed"), py::arg("gamma"), py::arg("beta"),
+        py::arg("running_mean"), py::arg("running_var"), py::arg("eps"), py::arg("momentum"), py::arg("out_dtype"),
+        py::arg("out") = py::none());
+  m.def("bn_apply_eval", &bn_apply_eval, py::arg("x"), py::arg("running_mean"), py::arg("running_var"),
+        py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("out_dtype"), py::arg("out") = py::none());
+  m.def("bn_bwd_reduce", &bn_bwd_reduce, py::arg("dy"), py::arg("x"), py::arg("stats"), py::arg("gamma"),
+        py::arg("dgamma") = py::none(), py::arg("dbeta") = py::none());
+  m.def("bn_bwd_dx", &bn_bwd_dx, py::arg("dy"), py::arg("x"), py::arg("stats"), py::arg("gamma"), py::arg("packed_g"),
+        py::arg("n"), py::arg("out") = py::none());
+  m.def("bn_chunk_rows", &jm_bn_chunk_rows, "rows per workgroup of the BatchNorm kernels");
+  m.def("bn_block_cols", &jm_bn_block_cols, "columns per workgroup of the BatchNorm kernels");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

@@ -314,3 +314,30 @@ int jm_cls_loss_bwd(const void* logits, int bf16, long ld, const int64_t* labels
                     double smoothing, int mode, int B, int L, const float* lse, const float* dloss, void* dlogits,
                     long ldo, hipStream_t st);
 int jm_debug_line_loss();
+
+// ---- batchnorm.hip (x: fp32 [B, J], rows ld >= J elements apart, any 4-byte-aligned base; gamma / beta / running
+// statistics fp32 [J]; part: fp64 [jm_bn_chunks(B), 2, J] workspace; -1 bad argument, -2 failed launch)
+// row chunks of a batch (= rows of part), rows per chunk, columns per workgroup
+int jm_bn_chunks(int B);
+int jm_bn_chunk_rows();
+int jm_bn_block_cols();
+// packed fp32 [2 J] = [mean, mean of squares] over the B rows
+int jm_bn_stats(const float* x, long ld, int B, int J, double* part, float* packed, hipStream_t st);
+// y (bf16 or fp32, rows ldy apart) = (x - mean) rstd gamma + beta with var = max(0, mean2 - mean^2) from packed;
+// stats fp32 [2 J] = [mean, rstd]; running = momentum running + (1 - momentum) (mean, var), in place
+int jm_bn_apply(const float* x, long ld, int B, int J, const float* packed, const float* gamma, const float* beta,
+                double eps, double momentum, void* y, int y_bf16, long ldy, float* stats, float* running_mean,
+                float* running_var, hipStream_t st);
+// the same from the running statistics; writes y only
+int jm_bn_apply_eval(const float* x, long ld, int B, int J, const float* running_mean, const float* running_var,
+                     const float* gamma, const float* beta, double eps, void* y, int y_bf16, long ldy,
+                     hipStream_t st);
+// dbeta = colsum(dy), dgamma = colsum(dy xhat) (accum: added to them), packed_g fp32 [2 J] = gamma times both;
+// dy bf16 or fp32, rows lddy apart
+int jm_bn_bwd_reduce(const void* dy, int dy_bf16, long lddy, const float* x, long ld, int B, int J,
+                     const float* stats, const float* gamma, double* part, float* dgamma, float* dbeta, int accum,
+                     float* packed_g, hipStream_t st);
+// dx (fp32, rows lddx apart) = rstd (gamma dy - packed_g[0] / n - xhat packed_g[1] / n), n = the global batch
+int jm_bn_bwd_dx(const void* dy, int dy_bf16, long lddy, const float* x, long ld, int B, int J, const float* stats,
+                 const float* gamma, const float* packed_g, double n, float* dx, long lddx, hipStream_t st);
+int jm_debug_line_batchnorm();

@@ -498,8 +498,10 @@ class LinearCLS:
         """fp32 logits; ``raw``: the Dense's own output in the compute dtype (no fp32 copy)."""
         if self.batch_norm:
             from ..parallel.syncbn import sync_batch_norm
+            # the fused GPU path writes the compute dtype itself: the cast below is then a no-op
             x = sync_batch_norm(x, self.bn_scale, self.bn_bias, self.running_mean, self.running_var,
-                                training=not det, momentum=0.99, eps=1e-5, group=group)
+                                training=not det, momentum=0.99, eps=1e-5, group=group,
+                                out_dtype=self.dense.k.store.compute_dtype)
         dt = self.dense.k.store.compute_dtype
         y = self.dense(x.to(dt))
         return y if raw else y.float()
