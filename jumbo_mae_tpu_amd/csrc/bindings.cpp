@@ -615,6 +615,65 @@ torch::Tensor patch_mse_bwd(torch::Tensor pred, torch::Tensor img, torch::Tensor
   return dpred;
 }
 
+// reconstruction panels (recon.hip) -> (recon, paste, masked uint8 [B, 3, H, W], err fp32 [B, N]).
+// pred: bf16 or fp32 [B*N, 3p^2]; mask: fp32 [N] (shared) or [B, N], 1 = masked; out: the four outputs to
+// write into instead of new tensors.  Everything is checked before any pointer reaches the kernel.
+std::vector<torch::Tensor> recon(torch::Tensor pred, torch::Tensor images, torch::Tensor mask, int64_t p, bool norm_pix,
+                                 int64_t fill, c10::optional<std::vector<torch::Tensor>> out) {
+  CHECK_CUDA(pred);
+  CHECK_CUDA(images);
+  CHECK_CUDA(mask);
+  TORCH_CHECK(images.device() == pred.device() && mask.device() == pred.device(), "recon: tensors on one device");
+  TORCH_CHECK(pred.scalar_type() == torch::kBFloat16 || pred.scalar_type() == torch::kFloat32,
+              "recon: pred must be bf16 or fp32");
+  CHECK_DT(images, torch::kUInt8);
+  CHECK_DT(mask, torch::kFloat32);
+  CHECK_CONTIG(pred);
+  CHECK_CONTIG(images);
+  CHECK_CONTIG(mask);
+  TORCH_CHECK(pred.dim() == 2, "recon: pred [B*N, 3p^2]");
+  TORCH_CHECK(images.dim() == 4 && images.size(1) == 3, "recon: images [B, 3, H, W]");
+  TORCH_CHECK(fill >= 0 && fill <= 255, "recon: fill is a byte");
+  const int64_t B = images.size(0), H = images.size(2), W = images.size(3);
+  TORCH_CHECK(p > 0 && p % 2 == 0, "recon: patch size must be positive and even, got ", p);
+  TORCH_CHECK(H > 0 && W > 0 && H % p == 0 && W % p == 0, "recon: image ", H, " x ", W,
+              " is not a whole number of ", p, " x ", p, " patches");
+  TORCH_CHECK(H <= INT_MAX && W <= INT_MAX && B <= INT_MAX, "recon: image batch too large");
+  const int64_t N = (H / p) * (W / p);
+  TORCH_CHECK(B * N <= INT_MAX, "recon: too many patches");
+  TORCH_CHECK(pred.size(0) == B * N && pred.size(1) == 3 * p * p, "recon: pred must be [", B * N, ", ", 3 * p * p,
+              "], got [", pred.size(0), ", ", pred.size(1), "]");
+  TORCH_CHECK((mask.dim() == 1 && mask.size(0) == N) || (mask.dim() == 2 && mask.size(0) == B && mask.size(1) == N),
+              "recon: mask must be [", N, "] or [", B, ", ", N, "]");
+  const long maskB = mask.dim() == 1 ? 0 : (long)N;
+  torch::Tensor rec, paste, masked, err;
+  if (out.has_value()) {
+    TORCH_CHECK(out->size() == 4, "recon: out = (recon, paste, masked, err)");
+    for (int i = 0; i < 3; ++i) {
+      const auto& t = (*out)[i];
+      TORCH_CHECK(t.is_cuda() && t.device() == pred.device() && t.scalar_type() == torch::kUInt8 &&
+                      t.is_contiguous() && t.sizes() == images.sizes(),
+                  "recon: out[", i, "] must be a contiguous uint8 tensor shaped like images");
+    }
+    const auto& e = (*out)[3];
+    TORCH_CHECK(e.is_cuda() && e.device() == pred.device() && e.scalar_type() == torch::kFloat32 &&
+                    e.is_contiguous() && e.dim() == 2 && e.size(0) == B && e.size(1) == N,
+                "recon: out[3] must be a contiguous fp32 [B, N] tensor");
+    rec = (*out)[0], paste = (*out)[1], masked = (*out)[2], err = e;
+  } else {
+    rec = torch::empty_like(images);
+    paste = torch::empty_like(images);
+    masked = torch::empty_like(images);
+    err = torch::empty({B, N}, images.options().dtype(torch::kFloat32));
+  }
+  check_rc(jm_recon(pred.data_ptr(), pred.scalar_type() == torch::kBFloat16, images.data_ptr<uint8_t>(),
+                    mask.data_ptr<float>(), maskB, rec.data_ptr<uint8_t>(), paste.data_ptr<uint8_t>(),
+                    masked.data_ptr<uint8_t>(), err.data_ptr<float>(), (int)B, (int)H, (int)W, (int)p, norm_pix,
+                    (int)fill, stream()),
+           "recon");
+  return {rec, paste, masked, err};
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ GEMM
@@ -1418,7 +1477,8 @@ py::dict debug_lines() {
       {"elementwise", jm_debug_line_elementwise},
       {"gemm", jm_debug_line_gemm},           {"gemm_tn", jm_debug_line_gemm_tn},
       {"layernorm", jm_debug_line_layernorm}, {"loss", jm_debug_line_loss},
-      {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim}};
+      {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
+      {"recon", jm_debug_line_recon}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1522,6 +1582,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("patch_mse_fwd", &patch_mse_fwd);
   m.def("mix_patches", &mix_patches);
   m.def("patch_mse_bwd", &patch_mse_bwd);
+  m.def("recon", &recon, py::arg("pred"), py::arg("images"), py::arg("mask"), py::arg("p"), py::arg("norm_pix"),
+        py::arg("fill") = 127, py::arg("out") = py::none(),
+        "MAE reconstruction panels -> (recon, paste, masked uint8 [B, 3, H, W], err fp32 [B, N])");
   m.def("cls_loss_fwd", &cls_loss_fwd, py::arg("logits"), py::arg("labels"), py::arg("perm") = py::none(),
         py::arg("w") = py::none(), py::arg("smoothing") = 0.0, py::arg("mode") = 0);
   m.def("cls_loss_bwd", &cls_loss_bwd, py::arg("dloss"), py::arg("logits"), py::arg("labels"),

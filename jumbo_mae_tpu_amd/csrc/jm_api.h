@@ -228,6 +228,18 @@ int jm_patch_mse_bwd(const uint16_t* pred, long ldp, const uint8_t* img, const f
                      int N, int H, int W, int p, int norm_pix, hipStream_t st);
 int jm_debug_line_mae();
 
+// ---- recon.hip
+// reconstruction panels of pred [B*N, 3p^2] (bf16 or fp32, contiguous, (ph, pw, c) order) against the uint8
+// images [B, 3, H, W]: recon = every patch painted from pred, paste / masked = the original bytes on visible
+// patches and the recon bytes / the fill byte on masked ones (mask fp32, 1 = masked, image b's row at
+// b * maskB: 0 = one shared [N] mask, N = per-sample), err fp32 [B, N] = per-patch mean of
+// (x_clamped / 255 - orig / 255)^2 before rounding.  p = 16 on 4-byte aligned images with W % 4 == 0 moves
+// words, any other even p bytes; -1 bad argument (odd p, H % p, W % p, maskB), -2 failed launch
+int jm_recon(const void* pred, int pred_bf16, const uint8_t* img, const float* mask, long maskB, uint8_t* recon,
+             uint8_t* paste, uint8_t* masked, float* err, int B, int H, int W, int p, int norm_pix, int fill,
+             hipStream_t st);
+int jm_debug_line_recon();
+
 // ---- gemm.hip
 // C = A[M, K] . B[N, K]^T on the MFMA kernels with epilogue epi (GemmEpi)
 int jm_gemm_nt(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int epi,

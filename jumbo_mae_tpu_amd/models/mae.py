@@ -65,9 +65,10 @@ class PretrainModel:
             noise = torch.rand(shape, generator=noise_rng, device=self.device)
         return masking_ids(noise, self.cfg.keep_len)
 
-    def forward(self, images_u8: torch.Tensor, rngs: dict | None = None, det: bool = False,
-                noise: torch.Tensor | None = None, per_sample: bool = False) -> dict:
-        rngs = rngs or {}
+    def _predict(self, images_u8: torch.Tensor, rngs: dict, det: bool, enc_det: bool,
+                 noise: torch.Tensor | None):
+        """Mask, encode the kept patches, decode every patch: (pred [B, N, p*p*3], mask,
+        (ids_shuffle, ids_restore, ids_keep))."""
         cfg = self.cfg
         B = images_u8.shape[0]
         C = cfg.num_cls_tokens
@@ -77,20 +78,46 @@ class PretrainModel:
         rows = mae_ops.kept_patches(images_u8, ids_keep, cfg.patch_size, self.store.compute_dtype)
         drop = rngs.get("dropout")
         x = self.encoder.embed_rows(rows, ids_keep, B)
-        # encoder always runs with det=False (pretraining.py:92, quirk Q3)
-        x = self.encoder.blocks(x, drop, det=False)
+        x = self.encoder.blocks(x, drop, det=enc_det)
         h = self.encoder.norm(x)  # [B*(C+K), D]
         y = self.decoder_proj(h).view(B, C + K, -1)
         dec_in = mae_ops.unshuffle_fused(y, self.mask_token, ids_restore, self.decoder.posemb_table(y.device), C)
         xd = self.decoder.blocks(dec_in, drop, det=det)
         hd = self.decoder.dec_norm(xd, row0=C)  # [B*N, d] only patch rows are predicted
         pred = self.decoder_image_output(hd)  # [B*N, p*p*3]
+        return pred.view(B, N, -1), mask, (ids_shuffle, ids_restore, ids_keep)
+
+    def forward(self, images_u8: torch.Tensor, rngs: dict | None = None, det: bool = False,
+                noise: torch.Tensor | None = None, per_sample: bool = False) -> dict:
+        # encoder always runs with det=False (pretraining.py:92, quirk Q3)
+        pred, mask, _ = self._predict(images_u8, rngs or {}, det, False, noise)
         # target pixels come straight from the uint8 images (no fp32 patch tensor)
-        per_patch = mae_ops.patch_mse(pred.view(B, N, -1), images_u8, cfg.patch_size, self.norm_pix_loss)
+        per_patch = mae_ops.patch_mse(pred, images_u8, self.cfg.patch_size, self.norm_pix_loss)
         loss = mae_ops.masked_mean_loss(per_patch, mask, per_sample)
         return {"loss": loss}
 
     __call__ = forward
+
+    @torch.no_grad()
+    def reconstruct(self, images_u8: torch.Tensor, noise: torch.Tensor | None = None, rngs: dict | None = None,
+                    det: bool = True, fill: int = 127) -> dict:
+        """Reconstruction images and their pixel-space quality.
+
+        Returns ``recon`` / ``paste`` / ``masked`` (uint8 [B, 3, H, W], ops/mae.py
+        ``reconstruct_panels``), ``mask`` [B, N] (1 = masked), ``err`` [B, N] and ``psnr_masked``
+        [B] = -10 log10 of the mean of ``err`` over each image's masked patches ([0, 1] pixel scale,
+        clamped and unrounded), comparable between --norm-pix-loss on and off.  Encoder and decoder
+        both run with ``det`` (default True: a picture should not depend on a droppath draw).  No
+        stream of the training ``rngs`` is touched unless the caller passes it; without ``noise``
+        and without ``rngs["noise"]`` the mask comes from torch's default generator."""
+        B = images_u8.shape[0]
+        pred, mask, _ = self._predict(images_u8, rngs or {}, det, det, noise)
+        out = mae_ops.reconstruct_panels(pred, images_u8, mask, self.cfg.patch_size, self.norm_pix_loss, fill)
+        mask = (mask if mask.dim() == 2 else mask.unsqueeze(0).expand(B, mask.shape[0])).contiguous()
+        mse = (out["err"] * mask).sum(-1) / mask.sum(-1)
+        out["mask"] = mask
+        out["psnr_masked"] = -10.0 * torch.log10(mse)
+        return out
 
     @torch.no_grad()
     def evaluate(self, images_u8: torch.Tensor, valid: torch.Tensor | None = None, rngs: dict | None = None) -> dict:

@@ -221,6 +221,74 @@ def masked_mean_loss(per_patch: torch.Tensor, mask: torch.Tensor, per_sample: bo
     return (pp.mean(-1) / valid_ratio).mean()
 
 
+# ------------------------------------------------------------------ reconstruction panels
+def unpatchify(patches: torch.Tensor, p: int, H: int, W: int) -> torch.Tensor:
+    """[B, N, 3p^2] patches in (ph, pw, c) order -> [B, 3, H, W]; the inverse of
+    ``extract_patches_nchw``."""
+    B = patches.shape[0]
+    gh, gw = H // p, W // p
+    x = patches.reshape(B, gh, gw, p, p, 3)
+    return x.permute(0, 5, 1, 3, 2, 4).reshape(B, 3, H, W)
+
+
+def _pixel_mask(mask: torch.Tensor, B: int, p: int, H: int, W: int) -> torch.Tensor:
+    """Patch mask [N] or [B, N] (1 = masked) -> bool [B, 1, H, W]."""
+    gh, gw = H // p, W // p
+    m = (mask if mask.dim() == 2 else mask.unsqueeze(0).expand(B, gh * gw)) > 0
+    return m.reshape(B, 1, gh, gw).repeat_interleave(p, 2).repeat_interleave(p, 3)
+
+
+def reconstruct_torch(pred: torch.Tensor, images_u8: torch.Tensor, mask: torch.Tensor, p: int, norm_pix: bool,
+                      fill: int = 127, fp64: bool = False) -> dict:
+    """Reconstruction panels from the decoder's prediction, as a torch composition: the CPU path
+    and the oracle of csrc/recon.hip (``fp64=True``: the same math in float64 on the same fp32
+    normalisation constants and the prediction as stored).
+
+    pred [B*N, 3p^2] or [B, N, 3p^2] in (ph, pw, c) order; mask [N] or [B, N], 1 = masked.
+    With ``norm_pix`` the prediction lives in the per-patch normalized space of ``norm_pix`` and is
+    mapped back with the patch's own biased statistics: v = pred sqrt(var + 1e-6) + mean.  Then
+    x = (v std_c + mean_c) 255 clamped to [0, 255] (NaN -> 0); ``recon`` is x rounded half to even.
+    Returns ``recon`` / ``paste`` / ``masked`` (uint8 [B, 3, H, W]: paste and masked keep the original
+    bytes on visible patches and take the recon bytes / ``fill`` on masked ones), ``err`` [B, N] = the
+    per-patch mean of (x / 255 - orig / 255)^2 on the clamped UNROUNDED x, and ``x`` itself."""
+    dt = torch.float64 if fp64 else torch.float32
+    B, _, H, W = images_u8.shape
+    N = (H // p) * (W // p)
+    m, s = _mean_std(images_u8.device)
+    m, s = m.to(dt), s.to(dt)
+    orig = images_u8.to(dt) / 255.0
+    v = pred.to(dt).reshape(B, N, 3 * p * p)
+    if norm_pix:
+        t = extract_patches_nchw((orig - m) / s, p)
+        mean = t.mean(-1, keepdim=True)
+        var = t.var(-1, keepdim=True, unbiased=False)
+        v = v * torch.sqrt(var + 1e-6) + mean
+    x = (unpatchify(v, p, H, W) * s + m) * 255.0
+    x = torch.where(x > 0, x, torch.zeros_like(x)).clamp(max=255.0)  # NaN -> 0
+    recon = torch.round(x).to(torch.uint8)
+    err = extract_patches_nchw((x / 255.0 - orig).square(), p).mean(-1)
+    mpix = _pixel_mask(mask, B, p, H, W)
+    return {"recon": recon, "paste": torch.where(mpix, recon, images_u8),
+            "masked": torch.where(mpix, torch.full_like(images_u8, fill), images_u8), "err": err, "x": x}
+
+
+def reconstruct_panels(pred: torch.Tensor, images_u8: torch.Tensor, mask: torch.Tensor, p: int, norm_pix: bool,
+                       fill: int = 127) -> dict:
+    """``recon`` / ``paste`` / ``masked`` / ``err`` of ``reconstruct_torch``.  GPU: one HIP kernel
+    (csrc/recon.hip) reads pred and the uint8 images and writes all four; CPU: the composition."""
+    if _ext.use_hip(pred):
+        B = images_u8.shape[0]
+        pr = pred.reshape(-1, pred.shape[-1])
+        if pr.dtype != torch.bfloat16:
+            pr = pr.float()
+        rec, paste, masked, err = _ext.load().recon(pr.contiguous(), images_u8.contiguous(),
+                                                    mask.float().contiguous(), p, bool(norm_pix), fill)
+        return {"recon": rec, "paste": paste, "masked": masked, "err": err.view(B, -1)}
+    out = reconstruct_torch(pred, images_u8, mask, p, norm_pix, fill)
+    del out["x"]
+    return out
+
+
 def mixed_patches(images_u8: torch.Tensor, plan: dict | None, patch_size: int, dtype) -> torch.Tensor:
     """All patches of the normalized (Mixup / CutMix blended, ``utils.mixup.Mixup.plan``) batch as
     the patch-embed GEMM operand [B*N, p*p*3].  GPU: one HIP kernel from uint8 (K19 fused with

@@ -119,6 +119,7 @@ def _extensions(p: argparse.ArgumentParser):
     g.add_argument("--skip-nonfinite", action="store_true",
                    help="skip the update of a step whose loss is non-finite (one host sync per step); "
                         "default: abort at the next log step")
+    return g
 
 
 def pretrain_parser() -> argparse.ArgumentParser:
@@ -138,7 +139,11 @@ def pretrain_parser() -> argparse.ArgumentParser:
     for s in ("init", "mixup", "dropout", "noise", "shuffle"):
         p.add_argument(f"--{s}-seed", type=int, default=random.randint(0, 1000000))
     _optim(p)
-    _extensions(p)
+    ext = _extensions(p)
+    ext.add_argument("--recon-images", type=int, default=0,
+                     help="at every evaluation rank 0 reconstructs the first N validation images (mask from a private "
+                          "generator seeded with --noise-seed), writes {output_dir}/{name}-recon-{step:07d}.png "
+                          "(original | masked | reconstruction | pasted) and logs val/psnr_masked; 0 = off")
     p.add_argument("--mask-mode", default="shared", choices=["shared", "per-sample"],
                    help="shared: one permutation per rank per step (reference, Q1)")
     return p

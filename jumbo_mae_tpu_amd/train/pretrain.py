@@ -59,6 +59,54 @@ def evaluate(model, loader, rngs, device) -> dict:
     return {"val/loss": loss / max(n, 1.0)}
 
 
+def first_images(loader, n: int, device) -> torch.Tensor:
+    """The first ``n`` real (unpadded) images of a validation loader, uint8 [<= n, 3, S, S]."""
+    got, have = [], 0
+    for batch in C.DevicePrefetcher(loader, device):
+        images, labels = batch if isinstance(batch, (list, tuple)) else (batch, None)
+        if labels is not None:
+            images = images[labels != -1]
+        got.append(images[:n - have])
+        have += got[-1].shape[0]
+        if have >= n:
+            break
+    return torch.cat(got)
+
+
+def recon_panel(images_u8: torch.Tensor, out: dict):
+    """PIL image with one row per input image: original | masked | reconstruction | pasted."""
+    import numpy as np
+    from PIL import Image
+
+    cols = [images_u8, out["masked"], out["recon"], out["paste"]]
+    rows = torch.cat([c.permute(0, 2, 3, 1) for c in cols], 2)  # [B, S, 4 S, 3]
+    return Image.fromarray(np.ascontiguousarray(rows.reshape(-1, rows.shape[2], 3).cpu().numpy()))
+
+
+def evaluate_recon(model, loader, args, device, step: int, log) -> dict:
+    """--recon-images (rank 0 only, no collectives): reconstructs the first N validation images
+    under a mask drawn from a private generator seeded with --noise-seed -- the same patches at
+    every evaluation, and nothing taken from the training streams -- writes
+    ``{output_dir}/{name}-recon-{step:07d}.png`` and returns ``val/psnr_masked`` (their mean)."""
+    from ..utils import gopen
+
+    with torch.random.fork_rng(devices=[]):  # a loader iterator seeds its workers from the default generator
+        images = first_images(loader, args.recon_images, device)
+    B, n = images.shape[0], model.cfg.seq_patches
+    g = torch.Generator().manual_seed(args.noise_seed)
+    noise = torch.rand((n,) if model.mask_mode == "shared" else (B, n), generator=g).to(device)
+    out = model.reconstruct(images, noise=noise)
+    if gopen.is_local(args.output_dir or "."):
+        import os
+
+        os.makedirs(args.output_dir or ".", exist_ok=True)
+        path = os.path.join(args.output_dir or ".", f"{args.name or 'run'}-recon-{step:07d}.png")
+        recon_panel(images, out).save(path)
+    else:
+        log(f"[eval] --recon-images: remote --output-dir {args.output_dir}, reconstruction PNG skipped")
+    return {"val/psnr_masked": float(out["psnr_masked"].mean())}
+
+
 def main(args) -> dict:
     info = pdist.init_distributed(args.device)
     set_trace_ranges(args.trace_ranges)
@@ -87,6 +135,8 @@ def main(args) -> dict:
                     use_wandb=False if args.log_file_only else None)
     if valid_loader is not None:  # SANITATION CHECK (main_pretrain.py:53-54), skipped without a valid set (Q8)
         result.update(evaluate(model, valid_loader, rngs, device))
+        if args.recon_images > 0 and info.is_main:
+            result.update(evaluate_recon(model, valid_loader, args, device, start, log))
         logger.log(dict(result), start)
         log(f"[eval] step {start} {result}")
     meter = AverageMeter(use_latest=["learning_rate"])
@@ -127,6 +177,8 @@ def main(args) -> dict:
                 C.save_last(args, model, opt, step, rngs, postfix="best", per_rank=per_rank,
                             best={"val/loss": min_val_loss})
             if info.is_main:
+                if args.recon_images > 0:
+                    res.update(evaluate_recon(model, valid_loader, args, device, step, log))
                 res["val/loss/best"] = min_val_loss
                 res["processed_samples"] = step * args.train_batch_size
                 logger.log(res, step)
