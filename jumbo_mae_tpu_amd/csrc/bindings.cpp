@@ -553,11 +553,13 @@ std::vector<torch::Tensor> unshuffle_bwd(torch::Tensor dout, torch::Tensor ids_r
   const int rpb = 64;
   const int nb = jm_unshuffle_bwd_blocks(B, C, N, rpb);
   auto dy = torch::empty({B, C + K, d}, dout.options().dtype(torch::kBFloat16));
-  auto part = torch::empty({nb, d}, dout.options());
-  check_rc(jm_unshuffle_bwd(dout.data_ptr<float>(), ids_restore.data_ptr<int>(), sb, bfp(dy), part.data_ptr<float>(), B,
+  auto part = torch::empty({nb, d}, dout.options().dtype(torch::kFloat64));
+  check_rc(jm_unshuffle_bwd(dout.data_ptr<float>(), ids_restore.data_ptr<int>(), sb, bfp(dy), part.data_ptr<double>(), B,
                             C, K, N, d, rpb, stream()),
            "unshuffle_bwd");
-  return {dy, part};  // [nb, d] fp32 partials: the caller adds their column sums (colsum_add_f32)
+  // the kernel's per-block fp64 partials summed in fp64 and rounded once -> [1, d] fp32: cancelling
+  // columns keep one fp32 ulp; the caller adds it to the gradient (colsum_add_f32)
+  return {dy, part.sum(0, true).to(torch::kFloat32)};
 }
 
 // finetune input: [B*N, 3p^2] bf16 normalized patches of the (Mixup / CutMix) blended batch
@@ -607,7 +609,8 @@ torch::Tensor patch_mse_bwd(torch::Tensor pred, torch::Tensor img, torch::Tensor
   CHECK_CONTIG(dmse);
   CHECK_DT(dmse, torch::kFloat32);
   const int H = img.size(2), W = img.size(3), N = (H / p) * (W / p);
-  TORCH_CHECK(dmse.numel() == pred.size(0) && pred.size(0) == img.size(0) * N, "patch_mse_bwd shapes");
+  TORCH_CHECK(dmse.numel() == pred.size(0) && pred.size(0) == img.size(0) * N && pred.size(1) == 3 * p * p,
+              "patch_mse_bwd shapes");
   auto dpred = torch::empty({pred.size(0), pred.size(1)}, pred.options());
   check_rc(jm_patch_mse_bwd(bfp(pred), pred.stride(0), img.data_ptr<uint8_t>(), dmse.data_ptr<float>(), bfp(dpred),
                             pred.size(0), N, H, W, p, norm_pix, stream()),

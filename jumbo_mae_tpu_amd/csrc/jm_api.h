@@ -215,8 +215,8 @@ int jm_unshuffle_fwd(const uint16_t* y, const float* tok, const int* restore, lo
                      int B, int C, int K, int N, int d, hipStream_t st);
 // partial rows that jm_unshuffle_bwd writes to part
 int jm_unshuffle_bwd_blocks(int B, int C, int N, int rows_per_block);
-// its backward: dy for the kept tokens, per-block partial sums of the mask-token gradient
-int jm_unshuffle_bwd(const float* dout, const int* restore, long rsB, uint16_t* dy, float* part, int B, int C, int K,
+// its backward: dy for the kept tokens, per-block fp64 partial sums of the mask-token gradient
+int jm_unshuffle_bwd(const float* dout, const int* restore, long rsB, uint16_t* dy, double* part, int B, int C, int K,
                      int N, int d, int rows_per_block, hipStream_t st);
 // the patches of the mixup / cutmix of each image with image perm[b], bf16
 int jm_mix_patches(const uint8_t* img, const int* perm, const float* prm, const int* box, uint16_t* out, int B, int H,

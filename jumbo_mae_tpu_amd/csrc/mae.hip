@@ -3,29 +3,42 @@
 // patchify_normalize: uint8 NCHW images -> fp32 [B, N, p*p*3] patches of the normalized image,
 // element order (ph, pw, c) == extract_patches(NHWC) of the reference (utils_mae.py:67-73) after
 // ((x/255) - mean) / std (pretraining.py:90-91).  One workgroup per (image, patch row): the
-// 3 x p x W uint8 strip is staged through LDS with 4-byte loads, then written out coalesced.
+// 3 x p x W uint8 strip is staged through LDS with 4-byte loads (byte loads when the image base is
+// not 4-byte aligned: the host decides), then written out coalesced.
 #include "common.h"
 #include "jm_api.h"
 
 namespace {
 
 __constant__ float c_mean[3] = {0.485f, 0.456f, 0.406f};
-__constant__ float c_istd[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
+// ((u / 255) - mean_c) / std_c is formed with true (correctly rounded) divisions everywhere below:
+// the value of the fp32 torch composition bit for bit.  Multiplying by 1 / 255 and 1 / std instead
+// loses up to 35 x that composition's distance from fp64 where u / 255 nearly cancels against mean_c.
+__constant__ float c_std[3] = {0.229f, 0.224f, 0.225f};
 
 __global__ __launch_bounds__(256) void patchify_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H,
-                                                       int W, int p) {
+                                                       int W, int p, int word) {
   extern __shared__ __attribute__((aligned(16))) uint8_t strip[];  // [3][p][W]
   const int g = W / p;
   const int gh = H / p;
   const int b = blockIdx.x / gh, gy = blockIdx.x - (blockIdx.x / gh) * gh;
   const int W4 = W / 4;
-  for (int i = threadIdx.x; i < 3 * p * W4; i += 256) {
-    const int c = i / (p * W4);
-    const int rem = i - c * p * W4;
-    const int ph = rem / W4, x4 = rem - ph * W4;
-    const uint32_t v =
-        *reinterpret_cast<const uint32_t*>(img + (((long)b * 3 + c) * H + gy * p + ph) * W + x4 * 4);
-    *reinterpret_cast<uint32_t*>(strip + (c * p + ph) * W + x4 * 4) = v;
+  if (word) {
+    for (int i = threadIdx.x; i < 3 * p * W4; i += 256) {
+      const int c = i / (p * W4);
+      const int rem = i - c * p * W4;
+      const int ph = rem / W4, x4 = rem - ph * W4;
+      const uint32_t v =
+          *reinterpret_cast<const uint32_t*>(img + (((long)b * 3 + c) * H + gy * p + ph) * W + x4 * 4);
+      *reinterpret_cast<uint32_t*>(strip + (c * p + ph) * W + x4 * 4) = v;
+    }
+  } else {
+    for (int i = threadIdx.x; i < 3 * p * W; i += 256) {  // strip[i] = row (c, ph), pixel x
+      const int c = i / (p * W);
+      const int rem = i - c * p * W;
+      const int ph = rem / W, x = rem - ph * W;
+      strip[i] = img[(((long)b * 3 + c) * H + gy * p + ph) * W + x];
+    }
   }
   __syncthreads();
   const int KP = p * p * 3;
@@ -37,16 +50,21 @@ __global__ __launch_bounds__(256) void patchify_kernel(const uint8_t* __restrict
     const int r2 = k - ph * p * 3;
     const int pw = r2 / 3, c = r2 - (r2 / 3) * 3;
     const float v = (float)strip[(c * p + ph) * W + gx * p + pw];
-    o[idx] = (v * (1.f / 255.f) - c_mean[c]) * c_istd[c];
+    o[idx] = (v / 255.f - c_mean[c]) / c_std[c];
   }
 }
+
+inline bool aligned(const void* ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
 
 }  // namespace
 
 int jm_patchify_normalize(const uint8_t* img, float* out, int B, int H, int W, int p, hipStream_t st) {
-  if ((W % 4) || (H % p) || (W % p)) return -1;
+  if (p <= 0 || (H % p) || (W % p)) return -1;
   const size_t sm = (size_t)3 * p * W;
-  patchify_kernel<<<B * (H / p), 256, sm, st>>>(img, out, H, W, p);
+  if (sm > 64 * 1024) return -1;
+  if (B * (H / p) == 0) return 0;
+  // 4-byte loads need every image row 4-byte aligned: W % 4 == 0 and an aligned base; else by bytes
+  patchify_kernel<<<B * (H / p), 256, sm, st>>>(img, out, H, W, p, (W % 4 == 0 && aligned(img, 4)) ? 1 : 0);
   return 0;
 }
 
@@ -63,7 +81,7 @@ JM_DEVICE float patch_pixel(const uint8_t* __restrict__ img, int b, int H, int W
   const int r = o - ph * 3 * p;
   const int pw = r / 3, c = r - (r / 3) * 3;
   const float v = (float)img[(((long)b * 3 + c) * H + gy * p + ph) * W + gx * p + pw];
-  return (v * (1.f / 255.f) - c_mean[c]) * c_istd[c];
+  return (v / 255.f - c_mean[c]) / c_std[c];
 }
 
 // p = 16 (768 outputs per patch, one 64-lane row group per patch): lane l produces the 12
@@ -79,7 +97,7 @@ JM_DEVICE void p16_raw(const uint8_t* __restrict__ img, int b, int H, int W, int
 
 JM_DEVICE float p16_norm(const uint32_t* px, int j) {  // output j = 3 k + c of the lane
   const int k = j / 3, c = j - (j / 3) * 3;
-  return ((float)((px[c] >> (8 * k)) & 0xffu) * (1.f / 255.f) - c_mean[c]) * c_istd[c];
+  return ((float)((px[c] >> (8 * k)) & 0xffu) / 255.f - c_mean[c]) / c_std[c];
 }
 
 JM_DEVICE void p16_store12(uint16_t* o, const float* f) {
@@ -187,16 +205,18 @@ __global__ __launch_bounds__(256) void unshuffle_fwd_kernel(const uint16_t* __re
 // K13 backward in one pass over dout [B, C+N, d]: kept and CLS rows are gathered into dy
 // [B, C+K, d] (bf16, the decoder_proj GEMM operand); mask-token rows are summed into per-block
 // column partials part[blockIdx.x][d] (atomic-free, reduced by the caller).  Each block owns a
-// contiguous range of ``rows_per_block`` rows; threads cover 4 columns each.
+// contiguous range of ``rows_per_block`` rows; threads cover 4 columns each.  The sums and the
+// partials are fp64: the columns of dout cancel, and the mask-token gradient is held to one fp32
+// ulp of the exact sum, which fp32 partials cannot deliver.
 __global__ __launch_bounds__(256) void unshuffle_bwd_kernel(const float* __restrict__ dout, const int* __restrict__ restore,
-                                                            long rsB, uint16_t* __restrict__ dy, float* __restrict__ part,
+                                                            long rsB, uint16_t* __restrict__ dy, double* __restrict__ part,
                                                             int B, int C, int K, int N, int d, int rows_per_block) {
-  extern __shared__ float red[];  // [256 / q][d]
+  extern __shared__ double red[];  // [256 / q][d]
   const int q = d / 4;
   const int lanes = (256 / q) * q;
   const int col = (threadIdx.x % q) * 4;
   const int rg = threadIdx.x / q, nrg = 256 / q;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
   const long total = (long)B * (C + N);
   const long r0 = (long)blockIdx.x * rows_per_block;
   if (threadIdx.x < lanes) {
@@ -212,44 +232,55 @@ __global__ __launch_bounds__(256) void unshuffle_bwd_kernel(const float* __restr
           store4(dy + ((long)b * (C + K) + C + j) * d + col, f);
         } else {
 #pragma unroll
-          for (int u = 0; u < 4; ++u) acc[u] += f[u];
+          for (int u = 0; u < 4; ++u) acc[u] += (double)f[u];
         }
       }
     }
-    store4(red + rg * d + col, acc);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) red[rg * d + col + u] = acc[u];
   }
   __syncthreads();
   for (int c = threadIdx.x; c < d; c += 256) {
-    float s = 0.f;
+    double s = 0.0;
     for (int g = 0; g < nrg; ++g) s += red[g * d + c];
     part[(long)blockIdx.x * d + c] = s;
   }
 }
 
-// target pixels of one patch row for a wave: lane holds elements o = lane + 64 * j.  The patch's
-// 3 x p x p uint8 pixels are first staged into the wave's LDS slice with coalesced row loads
-// (p = 16: 48 lanes x 16 B), then each lane picks its (ph, pw, c) elements from LDS.
-template <int NJ, bool P16>
-JM_DEVICE void patch_target(const uint8_t* __restrict__ img, long row, int N, int H, int W, int p_, int P3_,
-                            bool norm_pix, uint8_t* lds, float* t) {
-  const int p = P16 ? 16 : p_, P3 = P16 ? 768 : P3_;
+// target pixels of one patch row for a wave (p != 16): lane holds elements o = lane + 64 * j.  The
+// patch's 3 x p x p uint8 pixels are first staged into the wave's LDS slice by bytes, then each
+// lane picks its (ph, pw, c) elements from LDS.
+//
+// The target, its norm_pix statistics, the squared error and the gradient are fp64 on the fp32
+// constants (as in recon.hip): the per-patch MSE is held to one fp32 ulp of the exact value wherever
+// the fp32 torch composition is that close, which fp32 sums over a patch do not deliver.  The
+// kernels stay bound by their loads and stores.  Wave sums are butterflies over fixed lane pairs
+// after a fixed per-lane order: reruns are bit-identical.
+__constant__ double c_istd64[3] = {1.0 / (double)0.229f, 1.0 / (double)0.224f, 1.0 / (double)0.225f};
+
+JM_DEVICE double norm_px64(uint32_t u, int c) {  // in fp64 the reciprocals cost 1e-16, cancellation included
+  return ((double)u * (1.0 / 255.0) - (double)c_mean[c]) * c_istd64[c];
+}
+
+// full-wave fp64 sum (the same value in every lane); requires all 64 lanes active
+JM_DEVICE double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
+  return v;
+}
+
+template <int NJ>
+JM_DEVICE void patch_target(const uint8_t* __restrict__ img, long row, int N, int H, int W, int p, int P3,
+                            bool norm_pix, uint8_t* lds, double* t) {
   const int g = W / p;
   const int b = (int)(row / N), n = (int)(row - (long)b * N);
   const int gy = n / g, gx = n - (n / g) * g;
   const int lane = threadIdx.x & 63;
   const uint8_t* src = img + ((long)b * 3 * H + gy * p) * W + gx * p;  // channel 0, first patch row
-  if (p == 16) {
-    if (lane < 48) {
-      const int c = lane >> 4, ph = lane & 15;
-      *reinterpret_cast<uint4*>(lds + lane * 16) =
-          *reinterpret_cast<const uint4*>(src + ((long)c * H + ph) * W);
-    }
-  } else {
-    for (int i = lane; i < P3; i += 64) {
-      const int c = i / (p * p), r = i - c * p * p;
-      const int ph = r / p, pw = r - (r / p) * p;
-      lds[i] = src[((long)c * H + ph) * W + pw];
-    }
+  for (int i = lane; i < P3; i += 64) {
+    const int c = i / (p * p), r = i - c * p * p;
+    const int ph = r / p, pw = r - (r / p) * p;
+    lds[i] = src[((long)c * H + ph) * W + pw];
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -258,27 +289,27 @@ JM_DEVICE void patch_target(const uint8_t* __restrict__ img, long row, int N, in
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int o = lane + 64 * j;
-    float v = 0.f;
+    double v = 0.0;
     if (o < P3) {
       const int ph = o / (3 * p), r = o - ph * 3 * p;
       const int pw = r / 3, c = r - (r / 3) * 3;
-      v = ((float)lds[(c * p + ph) * p + pw] * (1.f / 255.f) - c_mean[c]) * c_istd[c];
+      v = norm_px64(lds[(c * p + ph) * p + pw], c);
     }
     t[j] = v;
   }
   if (norm_pix) {  // per-patch (t - mean) / sqrt(var + 1e-6), biased var (pretraining.py:114-117)
-    float s = 0.f;
+    double s = 0.0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) s += t[j];
-    const float mean = wave_sum(s) / P3;
-    float v = 0.f;
+    const double mean = wave_sum_f64(s) / P3;
+    double v = 0.0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int o = lane + 64 * j;
-      const float dlt = o < P3 ? t[j] - mean : 0.f;
+      const double dlt = o < P3 ? t[j] - mean : 0.0;
       v += dlt * dlt;
     }
-    const float rs = rsqrtf(wave_sum(v) / P3 + 1e-6f);
+    const double rs = 1.0 / sqrt(wave_sum_f64(v) / P3 + 1e-6);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) t[j] = (t[j] - mean) * rs;
   }
@@ -289,7 +320,20 @@ JM_DEVICE void patch_target(const uint8_t* __restrict__ img, long row, int N, in
 // three 8-byte accesses per lane instead of twelve 2-byte ones, the pred loads are issued before
 // the pixel staging (both HBM round trips overlap), and each channel's 4 pixels come out of the
 // staged patch in one 4-byte LDS read.
-JM_DEVICE void p16_load_pred(const uint16_t* __restrict__ pr, float* f) {
+//
+// Every p = 16 call runs this form, so that the result does not depend on how pred or the image
+// happen to be laid out: ``vec`` (host) says which wide accesses are legal.  P16_PRED: pred rows
+// (and dpred) are 8-byte aligned (base and ldp % 4 == 0), else they move as 2-byte accesses;
+// P16_IMG: the image base is 16-byte aligned, else the patch is staged by bytes.  The arithmetic and
+// its order are the same in all four combinations.
+constexpr int P16_PRED = 1, P16_IMG = 2;
+
+JM_DEVICE void p16_load_pred(const uint16_t* __restrict__ pr, float* f, bool vec) {
+  if (!vec) {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) f[j] = bf2f(pr[j]);
+    return;
+  }
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     const uint2 v = *reinterpret_cast<const uint2*>(pr + 4 * q);
@@ -300,16 +344,20 @@ JM_DEVICE void p16_load_pred(const uint16_t* __restrict__ pr, float* f) {
   }
 }
 
-JM_DEVICE void p16_target(const uint8_t* __restrict__ img, long row, int N, int H, int W, bool norm_pix, uint8_t* lds,
-                          float* t) {
+JM_DEVICE void p16_target(const uint8_t* __restrict__ img, long row, int N, int H, int W, bool norm_pix, bool img16,
+                          uint8_t* lds, double* t) {
   const int g = W / 16;
   const int b = (int)(row / N), n = (int)(row - (long)b * N);
   const int gy = n / g, gx = n - (n / g) * g;
   const int lane = threadIdx.x & 63;
   const uint8_t* src = img + ((long)b * 3 * H + gy * 16) * W + gx * 16;
-  if (lane < 48) {
-    const int c = lane >> 4, ph = lane & 15;
-    *reinterpret_cast<uint4*>(lds + lane * 16) = *reinterpret_cast<const uint4*>(src + ((long)c * H + ph) * W);
+  if (img16) {  // W % 16 == 0: every patch row is 16-byte aligned with the base
+    if (lane < 48) {
+      const int c = lane >> 4, ph = lane & 15;
+      *reinterpret_cast<uint4*>(lds + lane * 16) = *reinterpret_cast<const uint4*>(src + ((long)c * H + ph) * W);
+    }
+  } else {  // the same LDS layout [c][ph][pw], byte by byte
+    for (int i = lane; i < 768; i += 64) lds[i] = src[((long)(i >> 8) * H + ((i >> 4) & 15)) * W + (i & 15)];
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -321,17 +369,17 @@ JM_DEVICE void p16_target(const uint8_t* __restrict__ img, long row, int N, int 
     const uint32_t px = *reinterpret_cast<const uint32_t*>(lds + (c * 16 + ph) * 16 + pw0);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      t[3 * k + c] = ((float)((px >> (8 * k)) & 0xffu) * (1.f / 255.f) - c_mean[c]) * c_istd[c];
+      t[3 * k + c] = norm_px64((px >> (8 * k)) & 0xffu, c);
   }
   if (norm_pix) {  // per-patch (t - mean) / sqrt(var + 1e-6), biased var (pretraining.py:114-117)
-    float s = 0.f;
+    double s = 0.0;
 #pragma unroll
     for (int j = 0; j < 12; ++j) s += t[j];
-    const float mean = wave_sum(s) * (1.f / 768.f);
-    float v = 0.f;
+    const double mean = wave_sum_f64(s) / 768.0;
+    double v = 0.0;
 #pragma unroll
     for (int j = 0; j < 12; ++j) v += (t[j] - mean) * (t[j] - mean);
-    const float rs = rsqrtf(wave_sum(v) * (1.f / 768.f) + 1e-6f);
+    const double rs = 1.0 / sqrt(wave_sum_f64(v) / 768.0 + 1e-6);
 #pragma unroll
     for (int j = 0; j < 12; ++j) t[j] = (t[j] - mean) * rs;
   }
@@ -342,36 +390,37 @@ JM_DEVICE void p16_target(const uint8_t* __restrict__ img, long row, int N, int 
 template <int NJ, bool P16>
 __global__ __launch_bounds__(256) void patch_mse_fwd_kernel(const uint16_t* __restrict__ pred, long ldp,
                                                             const uint8_t* __restrict__ img, float* __restrict__ mse,
-                                                            long rows, int N, int H, int W, int p, int norm_pix) {
+                                                            long rows, int N, int H, int W, int p, int norm_pix,
+                                                            int vec) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int P3 = 3 * p * p;
   __shared__ __attribute__((aligned(16))) uint8_t pix[4][64 * NJ];
-  float t[NJ];
+  double t[NJ];
   const int lane = threadIdx.x & 63;
-  if constexpr (P16) {  // ldp % 4 == 0 (host)
+  if constexpr (P16) {
     float f[12];
-    p16_load_pred(pred + row * ldp + 12 * lane, f);
-    p16_target(img, row, N, H, W, norm_pix != 0, pix[threadIdx.x >> 6], t);
-    float s = 0.f;
+    p16_load_pred(pred + row * ldp + 12 * lane, f, vec & P16_PRED);
+    p16_target(img, row, N, H, W, norm_pix != 0, vec & P16_IMG, pix[threadIdx.x >> 6], t);
+    double s = 0.0;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) s += (t[j] - f[j]) * (t[j] - f[j]);
-    s = wave_sum(s);
-    if (lane == 0) mse[row] = s * (1.f / 768.f);
+    for (int j = 0; j < 12; ++j) s += (t[j] - (double)f[j]) * (t[j] - (double)f[j]);
+    s = wave_sum_f64(s);
+    if (lane == 0) mse[row] = (float)(s / 768.0);
     return;
   }
-  patch_target<NJ, P16>(img, row, N, H, W, p, P3, norm_pix != 0, pix[threadIdx.x >> 6], t);
-  float s = 0.f;
+  patch_target<NJ>(img, row, N, H, W, p, P3, norm_pix != 0, pix[threadIdx.x >> 6], t);
+  double s = 0.0;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int o = lane + 64 * j;
     if (o < P3) {
-      const float dlt = t[j] - bf2f(pred[row * ldp + o]);
+      const double dlt = t[j] - (double)bf2f(pred[row * ldp + o]);
       s += dlt * dlt;
     }
   }
-  s = wave_sum(s);
-  if (lane == 0) mse[row] = s / P3;
+  s = wave_sum_f64(s);
+  if (lane == 0) mse[row] = (float)(s / P3);
 }
 
 // K14 backward: dpred[row] = dmse[row] * 2 / P3 * (pred - t); rows with dmse == 0 (the kept,
@@ -380,41 +429,56 @@ template <int NJ, bool P16>
 __global__ __launch_bounds__(256) void patch_mse_bwd_kernel(const uint16_t* __restrict__ pred, long ldp,
                                                             const uint8_t* __restrict__ img,
                                                             const float* __restrict__ dmse, uint16_t* __restrict__ dpred,
-                                                            long rows, int N, int H, int W, int p, int norm_pix) {
+                                                            long rows, int N, int H, int W, int p, int norm_pix,
+                                                            int vec) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int P3 = 3 * p * p;
   const int lane = threadIdx.x & 63;
   const float gsc = dmse[row];
   __shared__ __attribute__((aligned(16))) uint8_t pix[4][64 * NJ];
-  float t[NJ];
-  if constexpr (P16) {  // ldp % 4 == 0 (host)
-    uint2* o = reinterpret_cast<uint2*>(dpred + row * 768 + 12 * lane);
+  double t[NJ];
+  if constexpr (P16) {
+    const bool pv = vec & P16_PRED;
+    uint16_t* o1 = dpred + row * 768 + 12 * lane;
+    uint2* o = reinterpret_cast<uint2*>(o1);
     if (gsc == 0.f) {
+      if (pv) {
 #pragma unroll
-      for (int q = 0; q < 3; ++q) o[q] = make_uint2(0u, 0u);
+        for (int q = 0; q < 3; ++q) o[q] = make_uint2(0u, 0u);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) o1[j] = 0;
+      }
       return;
     }
     float f[12];
-    p16_load_pred(pred + row * ldp + 12 * lane, f);
-    p16_target(img, row, N, H, W, norm_pix != 0, pix[threadIdx.x >> 6], t);
-    const float k = 2.f * gsc * (1.f / 768.f);
+    p16_load_pred(pred + row * ldp + 12 * lane, f, pv);
+    p16_target(img, row, N, H, W, norm_pix != 0, vec & P16_IMG, pix[threadIdx.x >> 6], t);
+    const double k = 2.0 * (double)gsc / 768.0;
+    float r[12];
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-      o[q] = make_uint2(pack_bf2(k * (f[4 * q] - t[4 * q]), k * (f[4 * q + 1] - t[4 * q + 1])),
-                        pack_bf2(k * (f[4 * q + 2] - t[4 * q + 2]), k * (f[4 * q + 3] - t[4 * q + 3])));
+    for (int j = 0; j < 12; ++j) r[j] = (float)(k * ((double)f[j] - t[j]));
+    if (pv) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        o[q] = make_uint2(pack_bf2(r[4 * q], r[4 * q + 1]), pack_bf2(r[4 * q + 2], r[4 * q + 3]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 12; ++j) o1[j] = f2bf(r[j]);
+    }
     return;
   }
   if (gsc == 0.f) {
     for (int o = lane; o < P3; o += 64) dpred[row * P3 + o] = 0;
     return;
   }
-  patch_target<NJ, P16>(img, row, N, H, W, p, P3, norm_pix != 0, pix[threadIdx.x >> 6], t);
-  const float k = 2.f * gsc / P3;
+  patch_target<NJ>(img, row, N, H, W, p, P3, norm_pix != 0, pix[threadIdx.x >> 6], t);
+  const double k = 2.0 * (double)gsc / P3;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int o = lane + 64 * j;
-    if (o < P3) dpred[row * P3 + o] = f2bf(k * (bf2f(pred[row * ldp + o]) - t[j]));
+    if (o < P3) dpred[row * P3 + o] = f2bf((float)(k * ((double)bf2f(pred[row * ldp + o]) - t[j])));
   }
 }
 
@@ -458,11 +522,11 @@ int jm_unshuffle_bwd_blocks(int B, int C, int N, int rows_per_block) {
   return cdiv((long)B * (C + N), rows_per_block);
 }
 
-int jm_unshuffle_bwd(const float* dout, const int* restore, long rsB, uint16_t* dy, float* part, int B, int C, int K,
+int jm_unshuffle_bwd(const float* dout, const int* restore, long rsB, uint16_t* dy, double* part, int B, int C, int K,
                      int N, int d, int rows_per_block, hipStream_t st) {
   if (d % 4 || d / 4 > 256) return -1;
   const int nb = jm_unshuffle_bwd_blocks(B, C, N, rows_per_block);
-  const size_t sm = (size_t)(256 / (d / 4)) * d * sizeof(float);
+  const size_t sm = (size_t)(256 / (d / 4)) * d * sizeof(double);
   unshuffle_bwd_kernel<<<nb, 256, sm, st>>>(dout, restore, rsB, dy, part, B, C, K, N, d, rows_per_block);
   return 0;
 }
@@ -472,13 +536,15 @@ int jm_patch_mse_fwd(const uint16_t* pred, long ldp, const uint8_t* img, float* 
   const int P3 = 3 * p * p;
   if (H % p || W % p || P3 > 64 * 16) return -1;
   const int nb = cdiv(rows, 4);
-  if (p == 16 && ldp % 4 == 0 && (reinterpret_cast<uintptr_t>(pred) & 7) == 0)
-    patch_mse_fwd_kernel<12, true><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix);
-  else if (P3 <= 64 * 4)
-    patch_mse_fwd_kernel<4, false><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix);
+  if (nb == 0) return 0;
+  if (p == 16) {
+    const int vec = (ldp % 4 == 0 && aligned(pred, 8) ? P16_PRED : 0) | (aligned(img, 16) ? P16_IMG : 0);
+    patch_mse_fwd_kernel<12, true><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix, vec);
+  } else if (P3 <= 64 * 4)
+    patch_mse_fwd_kernel<4, false><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix, 0);
   else if (P3 <= 64 * 12)
-    patch_mse_fwd_kernel<12, false><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix);
-  else patch_mse_fwd_kernel<16, false><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix);
+    patch_mse_fwd_kernel<12, false><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix, 0);
+  else patch_mse_fwd_kernel<16, false><<<nb, 256, 0, st>>>(pred, ldp, img, mse, rows, N, H, W, p, norm_pix, 0);
   return 0;
 }
 
@@ -487,14 +553,17 @@ int jm_patch_mse_bwd(const uint16_t* pred, long ldp, const uint8_t* img, const f
   const int P3 = 3 * p * p;
   if (H % p || W % p || P3 > 64 * 16) return -1;
   const int nb = cdiv(rows, 4);
-  if (p == 16 && ldp % 4 == 0 && (reinterpret_cast<uintptr_t>(pred) & 7) == 0)
-    patch_mse_bwd_kernel<12, true><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix);
-  else if (P3 <= 64 * 4)
-    patch_mse_bwd_kernel<4, false><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix);
+  if (nb == 0) return 0;
+  if (p == 16) {
+    const int vec =
+        (ldp % 4 == 0 && aligned(pred, 8) && aligned(dpred, 8) ? P16_PRED : 0) | (aligned(img, 16) ? P16_IMG : 0);
+    patch_mse_bwd_kernel<12, true><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix, vec);
+  } else if (P3 <= 64 * 4)
+    patch_mse_bwd_kernel<4, false><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix, 0);
   else if (P3 <= 64 * 12)
-    patch_mse_bwd_kernel<12, false><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix);
+    patch_mse_bwd_kernel<12, false><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix, 0);
   else
-    patch_mse_bwd_kernel<16, false><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix);
+    patch_mse_bwd_kernel<16, false><<<nb, 256, 0, st>>>(pred, ldp, img, dmse, dpred, rows, N, H, W, p, norm_pix, 0);
   return 0;
 }
 

@@ -201,7 +201,8 @@ class _PatchMSE(torch.autograd.Function):
 def patch_mse(pred: torch.Tensor, images_u8: torch.Tensor, patch_size: int, norm_pix_loss: bool) -> torch.Tensor:
     """mean_pix (target - pred)^2 per patch, [B, N] fp32 (utils_mae.py:51-64 before masking)."""
     B = images_u8.shape[0]
-    if _ext.use_hip(pred) and pred.dtype == torch.bfloat16 and pred.stride(-1) == 1:
+    fits = 3 * patch_size * patch_size <= 1024  # one wave holds a patch in 16 elements per lane (csrc/mae.hip)
+    if fits and _ext.use_hip(pred) and pred.dtype == torch.bfloat16 and pred.stride(-1) == 1:
         return _PatchMSE.apply(pred, images_u8, patch_size, bool(norm_pix_loss))
     t = normalized_patches(images_u8, patch_size)
     if norm_pix_loss:
