@@ -1471,6 +1471,97 @@ torch::Tensor bn_bwd_dx(torch::Tensor dy, torch::Tensor x, torch::Tensor stats, 
   return dx;
 }
 
+// ------------------------------------------------------------------------------ k-NN monitor
+static void check_knn_rows(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 && t.dim() == 2, "knn_topk: ", what, " must be bf16 [N, D]");
+  TORCH_CHECK(t.size(1) >= 1 && t.stride(1) == 1, "knn_topk: ", what, " must have a unit column stride");
+  TORCH_CHECK(t.size(0) <= 1 || t.stride(0) >= t.size(1), "knn_topk: ", what, " rows must not overlap");
+  TORCH_CHECK(t.size(0) < INT_MAX && t.size(1) < INT_MAX, "knn_topk: ", what, " too large");
+}
+
+// a caller's [Nq, cols] output: contiguous, on the device of q
+static void check_knn_out(const torch::Tensor& t, const torch::Tensor& q, int64_t rows, int64_t cols,
+                          torch::ScalarType dt, const char* fn, const char* what) {
+  TORCH_CHECK(t.scalar_type() == dt && t.dim() == 2 && t.size(0) == rows && t.size(1) == cols && t.is_contiguous() &&
+                  t.device() == q.device(),
+              fn, ": ", what, " must be a contiguous [Nq, ", cols, "] tensor of the right dtype on the inputs' device");
+}
+
+// (idx int32 [Nq, k], sim fp32 [Nq, k]); out_idx / out_sim given: written in place
+std::vector<torch::Tensor> knn_topk(torch::Tensor q, torch::Tensor bank, int64_t k,
+                                    c10::optional<torch::Tensor> self_idx, int64_t splits,
+                                    c10::optional<torch::Tensor> out_idx, c10::optional<torch::Tensor> out_sim) {
+  check_knn_rows(q, "q");
+  check_knn_rows(bank, "bank");
+  TORCH_CHECK(q.size(1) == bank.size(1), "knn_topk: q and bank must have the same D");
+  TORCH_CHECK(q.size(1) % 32 == 0, "knn_topk: D must be a multiple of 32");
+  TORCH_CHECK(k >= 1 && k <= 64, "knn_topk: k must be in 1..64");
+  TORCH_CHECK(splits >= 0 && splits <= 1024, "knn_topk: splits must be in 0..1024");
+  TORCH_CHECK(bank.size(0) >= 1, "knn_topk: the bank is empty");
+  TORCH_CHECK(bank.device() == q.device(), "knn_topk: q and bank must be on one device");
+  const int64_t Nq = q.size(0), Nb = bank.size(0);
+  const int* sp = nullptr;
+  if (self_idx.has_value() && self_idx->defined()) {
+    TORCH_CHECK(self_idx->scalar_type() == torch::kInt32 && self_idx->dim() == 1 && self_idx->size(0) == Nq &&
+                    self_idx->is_contiguous() && self_idx->device() == q.device(),
+                "knn_topk: self_idx must be int32 [Nq] on the inputs' device");
+    sp = self_idx->data_ptr<int>();
+  }
+  const bool has_out = out_idx.has_value() && out_idx->defined();
+  TORCH_CHECK(has_out == (out_sim.has_value() && out_sim->defined()), "knn_topk: out_idx and out_sim come together");
+  if (has_out) {
+    check_knn_out(*out_idx, q, Nq, k, torch::kInt32, "knn_topk", "out_idx");
+    check_knn_out(*out_sim, q, Nq, k, torch::kFloat32, "knn_topk", "out_sim");
+  }
+  TORCH_CHECK(q.is_cuda(), "knn_topk: q must be a GPU tensor");
+  auto idx = has_out ? *out_idx : torch::empty({Nq, k}, q.options().dtype(torch::kInt32));
+  auto sim = has_out ? *out_sim : torch::empty({Nq, k}, q.options().dtype(torch::kFloat32));
+  if (Nq == 0) return {idx, sim};
+  const int S = jm_knn_splits((int)Nq, (int)Nb, (int)splits);
+  TORCH_CHECK(S >= 1, "knn_topk: unsupported shape");
+  torch::Tensor sidx, ssim;
+  if (S > 1) {
+    sidx = torch::empty({S, Nq, k}, idx.options());
+    ssim = torch::empty({S, Nq, k}, sim.options());
+  }
+  check_rc(jm_knn_topk(q.data_ptr(), row_stride(q), bank.data_ptr(), row_stride(bank), sp, (int)Nq, (int)Nb,
+                       (int)q.size(1), (int)k, (int)splits, idx.data_ptr<int>(), sim.data_ptr<float>(),
+                       S > 1 ? sidx.data_ptr<int>() : nullptr, S > 1 ? ssim.data_ptr<float>() : nullptr, stream()),
+           "knn_topk");
+  return {idx, sim};
+}
+
+// (pred int32 [Nq, 5], hit1 bool [Nq], hit5 bool [Nq])
+std::vector<torch::Tensor> knn_vote(torch::Tensor idx, torch::Tensor sim, torch::Tensor bank_labels,
+                                    torch::Tensor labels, double T) {
+  TORCH_CHECK(idx.scalar_type() == torch::kInt32 && idx.dim() == 2 && idx.is_contiguous(),
+              "knn_vote: idx must be a contiguous int32 [Nq, k]");
+  TORCH_CHECK(sim.scalar_type() == torch::kFloat32 && sim.dim() == 2 && sim.is_contiguous() &&
+                  sim.size(0) == idx.size(0) && sim.size(1) == idx.size(1),
+              "knn_vote: sim must be a contiguous fp32 [Nq, k]");
+  const int64_t Nq = idx.size(0), k = idx.size(1);
+  TORCH_CHECK(k >= 1 && k <= 64, "knn_vote: k must be in 1..64");
+  TORCH_CHECK(bank_labels.scalar_type() == torch::kInt32 && bank_labels.dim() == 1 && bank_labels.is_contiguous() &&
+                  bank_labels.size(0) >= 1 && bank_labels.size(0) < INT_MAX,
+              "knn_vote: bank_labels must be a contiguous int32 [Nb]");
+  TORCH_CHECK(labels.scalar_type() == torch::kInt32 && labels.dim() == 1 && labels.is_contiguous() &&
+                  labels.size(0) == Nq && Nq < INT_MAX,
+              "knn_vote: labels must be a contiguous int32 [Nq]");
+  TORCH_CHECK(T > 0.0, "knn_vote: the temperature must be positive");
+  TORCH_CHECK(sim.device() == idx.device() && bank_labels.device() == idx.device() && labels.device() == idx.device(),
+              "knn_vote: all tensors must be on one device");
+  TORCH_CHECK(idx.is_cuda(), "knn_vote: idx must be a GPU tensor");
+  auto pred = torch::empty({Nq, 5}, idx.options());
+  auto hit1 = torch::empty({Nq}, idx.options().dtype(torch::kBool));
+  auto hit5 = torch::empty({Nq}, idx.options().dtype(torch::kBool));
+  check_rc(jm_knn_vote(idx.data_ptr<int>(), sim.data_ptr<float>(), bank_labels.data_ptr<int>(), labels.data_ptr<int>(),
+                       T, (int)Nq, (int)bank_labels.size(0), (int)k, pred.data_ptr<int>(),
+                       reinterpret_cast<uint8_t*>(hit1.data_ptr()), reinterpret_cast<uint8_t*>(hit5.data_ptr()),
+                       stream()),
+           "knn_vote");
+  return {pred, hit1, hit5};
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1481,7 +1572,7 @@ py::dict debug_lines() {
       {"gemm", jm_debug_line_gemm},           {"gemm_tn", jm_debug_line_gemm_tn},
       {"layernorm", jm_debug_line_layernorm}, {"loss", jm_debug_line_loss},
       {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
-      {"recon", jm_debug_line_recon}};
+      {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1592,6 +1683,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w") = py::none(), py::arg("smoothing") = 0.0, py::arg("mode") = 0);
   m.def("cls_loss_bwd", &cls_loss_bwd, py::arg("dloss"), py::arg("logits"), py::arg("labels"),
         py::arg("perm"), py::arg("w"), py::arg("smoothing"), py::arg("mode"), py::arg("lse"));
+  m.def("knn_topk", &knn_topk, py::arg("q"), py::arg("bank"), py::arg("k"), py::arg("self_idx") = py::none(),
+        py::arg("splits") = 0, py::arg("out_idx") = py::none(), py::arg("out_sim") = py::none(),
+        "fused similarity + top-k -> (idx int32, sim fp32) [Nq, k], ties by ascending bank index");
+  m.def("knn_splits", &jm_knn_splits, py::arg("Nq"), py::arg("Nb"), py::arg("splits") = 0,
+        "bank slices of a knn_topk launch");
+  m.def("knn_vote", &knn_vote, py::arg("idx"), py::arg("sim"), py::arg("bank_labels"), py::arg("labels"), py::arg("T"),
+        "weighted k-NN vote -> (pred int32 [Nq, 5], hit1, hit5 bool [Nq])");
   m.def("bn_stats", &bn_stats, py::arg("x"));
   m.def("bn_apply", &bn_apply, py::arg("x"), py::arg("packed"), py::arg("gamma"), py::arg("beta"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("eps"), py::arg("momentum"), py::arg("out_dtype"),

@@ -353,3 +353,19 @@ int jm_bn_bwd_reduce(const void* dy, int dy_bf16, long lddy, const float* x, lon
 int jm_bn_bwd_dx(const void* dy, int dy_bf16, long lddy, const float* x, long ld, int B, int J, const float* stats,
                  const float* gamma, const float* packed_g, double n, float* dx, long lddx, hipStream_t st);
 int jm_debug_line_batchnorm();
+
+// ---- knn.hip (q [Nq, D] / bank [Nb, D] bf16, 16-byte aligned rows ldq / ldb elements apart, D % 32 == 0,
+// 1 <= k <= 64; self_idx int32 [Nq] or null: the bank row a query skips, -1 = none)
+// idx int32 / sim fp32 [Nq, k]: per query the k largest dot products, sorted by (sim descending, bank index
+// ascending); missing entries idx = -1, sim = -inf.  splits 0 = chosen from the shape, > 0 = that many
+// contiguous bank slices; with more than one slice (jm_knn_splits) sidx / ssim [slices, Nq, k] are the scratch.
+// The result does not depend on splits.
+int jm_knn_splits(int Nq, int Nb, int splits);
+int jm_knn_topk(const void* q, long ldq, const void* bank, long ldb, const int* self_idx, int Nq, int Nb, int D, int k,
+                int splits, int* idx, float* sim, int* sidx, float* ssim, hipStream_t st);
+// weighted vote over the lists: w_j = exp((sim_j - sim_0) / T) in fp64 (idx -1 ignored), class scores added in
+// ascending j, ranked by (score descending, class id ascending).  pred int32 [Nq, 5] (-1 beyond the voted
+// classes), hit1 / hit5 bytes [Nq] (a label of -1 never hits)
+int jm_knn_vote(const int* idx, const float* sim, const int* bank_labels, const int* labels, double T, int Nq, int Nb,
+                int k, int* pred, uint8_t* hit1, uint8_t* hit5, hipStream_t st);
+int jm_debug_line_knn();

@@ -25,7 +25,7 @@ from ..ops import mae as mae_ops
 from ..ops import prims as P
 from ..utils.mixup import Mixup, smooth_labels
 from .params import ParamStore
-from .vit import JumboViT, LinearCLS
+from .vit import JumboViT, LinearCLS, cls_features
 
 
 def softmax_cross_entropy(logits, labels):
@@ -110,13 +110,7 @@ class FinetuneModel:
         return rows, labels
 
     def features(self, rows, B, rngs=None, det=True):
-        cfg = self.cfg
-        drop = rngs.get("dropout") if rngs else None
-        x = self.encoder.embed_rows(rows, None, B)
-        x = self.encoder.blocks(x, drop, det)
-        C = cfg.num_cls_tokens
-        h = Fn.layer_norm(x[:, :C], self.encoder.norm.g, self.encoder.norm.b, torch.float32)
-        return h.reshape(B, C * cfg.dim)
+        return cls_features(self.encoder, rows, B, rngs.get("dropout") if rngs else None, det)
 
     def logits(self, images_u8, labels=None, rngs=None, det=True, raw=False, plan=_DRAW):
         """(logits, mixed labels); ``raw``: the head's output in the compute dtype instead of fp32;

@@ -22,7 +22,7 @@ from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
 from ..ops import mae as mae_ops
 from ..utils.mae import masking_ids
 from .params import ParamStore, trunc_normal_
-from .vit import Dense, JumboViT, MAEDecoder
+from .vit import Dense, JumboViT, MAEDecoder, cls_features
 
 
 class PretrainModel:
@@ -118,6 +118,14 @@ class PretrainModel:
         out["mask"] = mask
         out["psnr_masked"] = -10.0 * torch.log10(mse)
         return out
+
+    @torch.no_grad()
+    def features(self, images_u8: torch.Tensor) -> torch.Tensor:
+        """[B, 3 * dim] fp32 encoder features as the classifier sees them: every patch (no masking),
+        ``det=True``, the final LayerNorm on the three CLS rows (``FinetuneModel.features`` on the
+        same parameters, bit for bit: both call ``cls_features``).  Touches no random stream."""
+        rows = mae_ops.mixed_patches(images_u8, None, self.cfg.patch_size, self.store.compute_dtype)
+        return cls_features(self.encoder, rows, images_u8.shape[0], None, True)
 
     @torch.no_grad()
     def evaluate(self, images_u8: torch.Tensor, valid: torch.Tensor | None = None, rngs: dict | None = None) -> dict:

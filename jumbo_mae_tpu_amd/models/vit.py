@@ -396,6 +396,18 @@ class JumboViT:
         return _run_layers(self.layers, x, rng, det, self.cfg.grad_ckpt, in_dropout=self.cfg.dropout)
 
 
+def cls_features(encoder: "JumboViT", rows: torch.Tensor, B: int, drop=None, det: bool = True) -> torch.Tensor:
+    """[B, C * dim] fp32: the encoder on every patch of ``rows`` ([B*N, p*p*3], compute dtype), then
+    the final LayerNorm on the C CLS rows alone (a per-row op: the same values as normalising every
+    row).  The features of ``FinetuneModel`` and of ``PretrainModel.features``."""
+    cfg = encoder.cfg
+    x = encoder.embed_rows(rows, None, B)
+    x = encoder.blocks(x, drop, det)
+    C = cfg.num_cls_tokens
+    h = Fn.layer_norm(x[:, :C], encoder.norm.g, encoder.norm.b, torch.float32)
+    return h.reshape(B, C * cfg.dim)
+
+
 def _run_layers(layers, x, rng, det, grad_ckpt, in_dropout=0.0):
     """The layer loop; consecutive fused blocks are chained by ``blocks.Link`` hand-offs (not
     under activation checkpointing, whose recompute would re-run forwards out of order).

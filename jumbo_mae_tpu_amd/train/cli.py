@@ -144,6 +144,11 @@ def pretrain_parser() -> argparse.ArgumentParser:
                      help="at every evaluation rank 0 reconstructs the first N validation images (mask from a private "
                           "generator seeded with --noise-seed), writes {output_dir}/{name}-recon-{step:07d}.png "
                           "(original | masked | reconstruction | pasted) and logs val/psnr_masked; 0 = off")
+    ext.add_argument("--knn-k", type=int, default=0,
+                     help="at every evaluation: weighted k-NN accuracy of the encoder features, leave-one-out on the "
+                          "validation set (val/knn_acc1, val/knn_acc5; needs validation labels); 1..64, 0 = off")
+    ext.add_argument("--knn-temperature", type=float, default=0.07,
+                     help="temperature T of the k-NN vote: neighbour j weighs exp((sim_j - sim_0) / T)")
     p.add_argument("--mask-mode", default="shared", choices=["shared", "per-sample"],
                    help="shared: one permutation per rank per step (reference, Q1)")
     return p

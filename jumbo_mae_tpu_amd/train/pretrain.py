@@ -21,6 +21,7 @@ import torch
 from ..config import DecoderConfig, ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.mae import PretrainModel
+from ..ops import knn as knn_ops
 from ..parallel import dist as pdist
 from ..utils.flops import pretrain_fwd_flops_per_image
 from ..utils.rng import RngStreams
@@ -45,18 +46,65 @@ def build_model(args, device, dtype) -> PretrainModel:
                          mask_mode=getattr(args, "mask_mode", "shared")).to(device, dtype, seed=args.init_seed)
 
 
-def evaluate(model, loader, rngs, device) -> dict:
+def evaluate(model, loader, rngs, device, knn_k: int = 0, knn_T: float = 0.07, log=None) -> dict:
+    """val/loss, and with ``knn_k`` > 0 (--knn-k) the k-NN monitor's val/knn_acc1 / val/knn_acc5 from
+    the same pass over the validation shard (``knn_metrics``)."""
     rngs = rngs.fork()  # validation never advances the training streams
     sums = None
+    feats, labs = [], []
     for batch in C.DevicePrefetcher(loader, device):
         images, labels = batch if isinstance(batch, (list, tuple)) else (batch, None)
         valid = (labels != -1) if labels is not None else None
         m = model.evaluate(images, valid, rngs.as_dict())
         sums = m if sums is None else {k: sums[k] + m[k] for k in m}
+        if knn_k > 0 and labels is not None:  # deterministic, no random stream: the loss above is unchanged
+            feats.append(knn_ops.normalize_features(model.features(images)))
+            labs.append(labels.to(torch.int64))
     packed = torch.stack([sums["loss"], sums["num_samples"]]).float()
     pdist.all_reduce_sum_(packed)
     loss, n = packed.tolist()
-    return {"val/loss": loss / max(n, 1.0)}
+    out = {"val/loss": loss / max(n, 1.0)}
+    if knn_k > 0:
+        if feats:
+            out.update(knn_metrics(torch.cat(feats), torch.cat(labs), knn_k, knn_T))
+        elif log is not None:
+            log("[eval] --knn-k: the validation loader yields no labels, k-NN monitor skipped")
+    return out
+
+
+def knn_metrics(feats: torch.Tensor, labels: torch.Tensor, k: int, T: float) -> dict:
+    """Leave-one-out weighted k-NN accuracy over the whole validation set (collective).
+
+    ``feats`` [n, D] bf16 normalised / ``labels`` [n] (-1 = padding) are this rank's shard.  The
+    ranks all-gather both, padded to the longest shard with label -1; each rank classifies its
+    own rows against the gathered bank, leaving out the row itself by its global index; hit sums
+    and the count travel in one packed all-reduce."""
+    import torch.distributed as dist
+
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    n = feats.shape[0]
+    self_idx = torch.arange(n, device=feats.device)
+    bank, bank_labels = feats, labels
+    if world > 1:
+        rank = dist.get_rank()
+        longest = torch.tensor([n], dtype=torch.int64, device=feats.device)
+        dist.all_reduce(longest, op=dist.ReduceOp.MAX)
+        L = int(longest.item())
+        f = torch.zeros(L, feats.shape[1], dtype=feats.dtype, device=feats.device)
+        y = torch.full((L,), -1, dtype=torch.int64, device=feats.device)
+        f[:n], y[:n] = feats, labels
+        fw = f.view(torch.uint8)  # the bytes: every backend gathers uint8
+        gf = torch.empty(world * L, fw.shape[1], dtype=torch.uint8, device=feats.device)
+        gy = torch.empty(world * L, dtype=torch.int64, device=feats.device)
+        dist.all_gather(list(gf.chunk(world)), fw)  # the chunks are views: gathered in place, in rank order
+        dist.all_gather(list(gy.chunk(world)), y)
+        bank, bank_labels = gf.view(feats.dtype), gy
+        self_idx = self_idx + rank * L
+    hit1, hit5 = knn_ops.knn_classify(feats, labels, k, T, bank, bank_labels, self_idx)
+    packed = torch.stack([hit1.sum(), hit5.sum(), (labels != -1).sum()]).double()
+    pdist.all_reduce_sum_(packed)
+    h1, h5, cnt = packed.tolist()
+    return {"val/knn_acc1": h1 / max(cnt, 1.0), "val/knn_acc5": h5 / max(cnt, 1.0)}
 
 
 def first_images(loader, n: int, device) -> torch.Tensor:
@@ -108,6 +156,10 @@ def evaluate_recon(model, loader, args, device, step: int, log) -> dict:
 
 
 def main(args) -> dict:
+    if args.knn_k:
+        knn_ops.check_k(args.knn_k)  # before any work: 1..64
+        if not args.knn_temperature > 0:
+            raise ValueError(f"--knn-temperature must be positive (got {args.knn_temperature})")
     info = pdist.init_distributed(args.device)
     set_trace_ranges(args.trace_ranges)
     device = info.device
@@ -134,7 +186,7 @@ def main(args) -> dict:
     logger = Logger(args.output_dir, args.name, args.project, vars(args), enabled=info.is_main,
                     use_wandb=False if args.log_file_only else None)
     if valid_loader is not None:  # SANITATION CHECK (main_pretrain.py:53-54), skipped without a valid set (Q8)
-        result.update(evaluate(model, valid_loader, rngs, device))
+        result.update(evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log))
         if args.recon_images > 0 and info.is_main:
             result.update(evaluate_recon(model, valid_loader, args, device, start, log))
         logger.log(dict(result), start)
@@ -171,7 +223,7 @@ def main(args) -> dict:
         # evaluation so that its sidecar carries the updated best metric
         per_rank = C.rank_states(rngs, model) if do_save else None
         if do_eval and valid_loader is not None:
-            res = evaluate(model, valid_loader, rngs, device)
+            res = evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log)
             if res["val/loss"] < min_val_loss:  # identical on every rank (all-reduced)
                 min_val_loss = res["val/loss"]
                 C.save_last(args, model, opt, step, rngs, postfix="best", per_rank=per_rank,
