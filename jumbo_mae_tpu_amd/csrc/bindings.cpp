@@ -437,6 +437,51 @@ void opt_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor trace, c10::optiona
              (float)momentum, stream());
 }
 
+// weight EMA: flat fp32 master / ema of one length on one GPU, an int32 [nchunks, 3] chunk table
+void check_ema_pair(const torch::Tensor& master, const torch::Tensor& ema, const torch::Tensor& rows,
+                    const char* fn) {
+  TORCH_CHECK(master.is_cuda() && ema.is_cuda() && rows.is_cuda() && ema.device() == master.device() &&
+                  rows.device() == master.device(),
+              fn, ": master, ema and rows must be tensors on one GPU");
+  TORCH_CHECK(master.scalar_type() == torch::kFloat32 && ema.scalar_type() == torch::kFloat32, fn,
+              ": master and ema must be fp32");
+  TORCH_CHECK(master.dim() == 1 && ema.dim() == 1 && master.is_contiguous() && ema.is_contiguous(), fn,
+              ": master and ema must be flat contiguous buffers");
+  TORCH_CHECK(ema.numel() == master.numel(), fn, ": ema has ", ema.numel(), " elements, the rows reach into master's ",
+              master.numel());
+  TORCH_CHECK(rows.scalar_type() == torch::kInt32 && rows.dim() == 2 && rows.size(1) == 3 && rows.is_contiguous(), fn,
+              ": rows must be a contiguous int32 [nchunks, 3] chunk table");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(ema.data_ptr()) % 16 == 0,
+              fn, ": master and ema must be 16-byte aligned");
+}
+
+void opt_ema(torch::Tensor master, torch::Tensor ema, torch::Tensor rows, torch::Tensor meta, torch::Tensor ema_hyper) {
+  check_ema_pair(master, ema, rows, "opt_ema");
+  TORCH_CHECK(meta.is_cuda() && meta.device() == master.device() && meta.scalar_type() == torch::kFloat32 &&
+                  meta.is_contiguous() && meta.dim() == 2 && meta.size(1) == 4,
+              "opt_ema: meta must be a contiguous fp32 [segments, 4] GPU tensor");
+  TORCH_CHECK(ema_hyper.is_cuda() && ema_hyper.device() == master.device() &&
+                  ema_hyper.scalar_type() == torch::kFloat32 && ema_hyper.numel() >= 1 && ema_hyper.is_contiguous(),
+              "opt_ema: ema_hyper must be an fp32 GPU tensor holding 1 - decay");
+  jm_opt_ema(master.data_ptr<float>(), ema.data_ptr<float>(), chp(rows), nch(rows), meta.data_ptr<float>(),
+             (int)meta.size(0), ema_hyper.data_ptr<float>(), (long)master.numel(), stream());
+}
+
+void ema_swap(torch::Tensor master, torch::Tensor ema, c10::optional<torch::Tensor> shadow, torch::Tensor rows) {
+  check_ema_pair(master, ema, rows, "ema_swap");
+  if (shadow.has_value() && shadow->defined()) {
+    TORCH_CHECK(shadow->is_cuda() && shadow->device() == master.device() &&
+                    shadow->scalar_type() == torch::kBFloat16 && shadow->is_contiguous(),
+                "ema_swap: shadow must be a contiguous bf16 tensor on master's GPU");
+    TORCH_CHECK(shadow->numel() == master.numel(), "ema_swap: shadow has ", shadow->numel(), " elements, master ",
+                master.numel());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(shadow->data_ptr()) % 8 == 0, "ema_swap: shadow must be 8-byte aligned");
+  }
+  jm_ema_swap(master.data_ptr<float>(), ema.data_ptr<float>(), shadow_ptr(shadow), chp(rows), nch(rows),
+              (long)master.numel(), stream());
+}
+
 // ------------------------------------------------------------------------------ MAE
 torch::Tensor patchify_normalize(torch::Tensor img, int64_t p) {
   CHECK_CONTIG(img);
@@ -1666,6 +1711,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("opt_lars_norms", &opt_lars_norms);
   m.def("opt_apply_trust", &opt_apply_trust);
   m.def("opt_sgd", &opt_sgd);
+  m.def("opt_ema", &opt_ema, py::arg("master"), py::arg("ema"), py::arg("rows"), py::arg("meta"),
+        py::arg("ema_hyper"));
+  m.def("ema_swap", &ema_swap, py::arg("master"), py::arg("ema"), py::arg("shadow"), py::arg("rows"));
   m.def("patchify_normalize", &patchify_normalize);
   m.def("gather_patches", &gather_patches);
   m.def("embed_finish", &embed_finish);

@@ -196,6 +196,12 @@ void jm_opt_apply_trust(float* p, const float* u_or_g, float* trace, uint16_t* s
 // one SGD (momentum) step
 void jm_opt_sgd(float* p, const float* g, float* trace, uint16_t* shadow, const int* chunks, int nchunks,
                 const float* meta, const float* hyper, const float* gnorm_sq, float momentum, hipStream_t st);
+// weight EMA on the rows of trainable segments: ema += ema_hyper[0] * (p - ema); n = elements of p and
+// ema, nseg = rows of meta (ema_kernel)
+void jm_opt_ema(const float* p, float* ema, const int* chunks, int nchunks, const float* meta, int nseg,
+                const float* ema_hyper, long n, hipStream_t st);
+// exchange p and ema on every row, bit for bit (+ the bf16 shadow copy of the new p) (ema_swap_kernel)
+void jm_ema_swap(float* p, float* ema, uint16_t* shadow, const int* chunks, int nchunks, long n, hipStream_t st);
 int jm_debug_line_optim();
 
 // ---- mae.hip

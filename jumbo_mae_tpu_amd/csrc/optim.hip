@@ -251,6 +251,78 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   }
 }
 
+// Weight EMA (optim/ema.py): e += omd * (p - e) on the rows of the optimizer update that has just
+// run, omd = 1 - decay from the device tensor ema_hyper (graph-capturable).  Reads p, writes only e;
+// frozen segments are skipped.  A zero increment (p == e, omd == 0, or a product that underflows)
+// keeps the bits of e, -0.0 included.  Same access pattern as adamw_kernel: 16 B per lane, the
+// chunk's last len % 4 elements in the scalar loop.  n = elements of p and e, nseg = rows of meta
+// (debug build: a row outside them is recorded and skipped).
+__global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ p, float* __restrict__ e,
+                                                  const Chunk* __restrict__ chunks, const float* __restrict__ meta,
+                                                  const float* __restrict__ ema_hyper, long n, int nseg) {
+  const Chunk c = chunks[blockIdx.x];
+  JM_DGUARD(c.start >= 0 && c.len >= 0 && (long)c.start + c.len <= n && (c.start & 3) == 0 && c.seg >= 0 &&
+            c.seg < nseg);
+  if (meta[4 * c.seg + 3] == 0.f) return;
+  const float omd = ema_hyper[0];
+  auto upd = [&](float pv, float ev) {
+    const float t = omd * (pv - ev);
+    return t == 0.f ? ev : ev + t;
+  };
+  const int n4 = c.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const long k = (long)c.start + 4L * i;
+    float pv[4], ev[4];
+    load4(p + k, pv);
+    load4(e + k, ev);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = upd(pv[j], ev[j]);
+    store4(e + k, ev);
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < c.len; i += 256) {
+    const long k = (long)c.start + i;
+    e[k] = upd(p[k], e[k]);
+  }
+}
+
+// bf16 of a moved fp32 word, round to nearest even; a NaN becomes the canonical 0x7FC0, which is what
+// the torch cast of the same value (ParamStore.sync_shadow) gives
+JM_DEVICE uint32_t bits2bf(uint32_t u) {
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+// Exchange p and e on every covered element and, with a shadow, write bf16(new p).  The words are
+// moved as integers: NaN payloads, infinities, -0.0 and subnormals keep their bits.  No meta: frozen
+// segments are exchanged too.
+__global__ __launch_bounds__(256) void ema_swap_kernel(uint32_t* __restrict__ p, uint32_t* __restrict__ e,
+                                                       uint16_t* __restrict__ shadow,
+                                                       const Chunk* __restrict__ chunks, long n) {
+  const Chunk c = chunks[blockIdx.x];
+  JM_DGUARD(c.start >= 0 && c.len >= 0 && (long)c.start + c.len <= n && (c.start & 3) == 0);
+  const int n4 = c.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const long k = (long)c.start + 4L * i;
+    const uint4 pv = *reinterpret_cast<const uint4*>(p + k);
+    const uint4 ev = *reinterpret_cast<const uint4*>(e + k);
+    *reinterpret_cast<uint4*>(p + k) = ev;
+    *reinterpret_cast<uint4*>(e + k) = pv;
+    if (shadow) {
+      uint2 s;
+      s.x = bits2bf(ev.x) | (bits2bf(ev.y) << 16);
+      s.y = bits2bf(ev.z) | (bits2bf(ev.w) << 16);
+      *reinterpret_cast<uint2*>(shadow + k) = s;
+    }
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < c.len; i += 256) {
+    const long k = (long)c.start + i;
+    const uint32_t pv = p[k], ev = e[k];
+    p[k] = ev;
+    e[k] = pv;
+    if (shadow) shadow[k] = (uint16_t)bits2bf(ev);
+  }
+}
+
 }  // namespace
 
 // cpart: nchunks (sumsq) / 2 * nchunks (LAMB / LARS norms) floats of chunk partials
@@ -290,6 +362,18 @@ void jm_opt_apply_trust(float* p, const float* u_or_g, float* trace, uint16_t* s
 void jm_opt_sgd(float* p, const float* g, float* trace, uint16_t* shadow, const int* chunks, int nchunks,
                 const float* meta, const float* hyper, const float* gnorm_sq, float momentum, hipStream_t st) {
   sgd_kernel<<<nchunks, 256, 0, st>>>(p, g, trace, shadow, (const Chunk*)chunks, meta, hyper, gnorm_sq, momentum);
+}
+
+void jm_opt_ema(const float* p, float* ema, const int* chunks, int nchunks, const float* meta, int nseg,
+                const float* ema_hyper, long n, hipStream_t st) {
+  if (nchunks < 1) return;
+  ema_kernel<<<nchunks, 256, 0, st>>>(p, ema, (const Chunk*)chunks, meta, ema_hyper, n, nseg);
+}
+
+void jm_ema_swap(float* p, float* ema, uint16_t* shadow, const int* chunks, int nchunks, long n, hipStream_t st) {
+  if (nchunks < 1) return;
+  ema_swap_kernel<<<nchunks, 256, 0, st>>>(reinterpret_cast<uint32_t*>(p), reinterpret_cast<uint32_t*>(ema), shadow,
+                                           (const Chunk*)chunks, n);
 }
 
 JM_DEBUG_EXPORT(optim)

@@ -92,6 +92,7 @@ class FlatOptimizer:
         self._shard = None       # GradReducer in ZeRO-1 mode: update only this rank's pieces
         self._owned_rows = None  # chunk-table rows of every owned piece
         self._owned_mask = None  # torch path: bool mask of owned elements
+        self.ema = None          # WeightEma following every update (attach_ema)
 
     # ---------------------------------------------------------------- helpers
     def _elem_meta(self):
@@ -113,6 +114,14 @@ class FlatOptimizer:
         if self._shard is not None:
             self._shard.sum_(out)
         return out
+
+    def attach_ema(self, ema) -> None:
+        """From now on ``ema`` (optim/ema.py ``WeightEma``) follows every parameter update on exactly
+        the rows it touched: ``prepare`` feeds its factor, each update path runs it right after the
+        parameter update, ``finish`` advances its count."""
+        assert ema.store is self.store
+        self.ema = ema
+        ema.opt = self
 
     # ---------------------------------------------------------------- step
     def step(self) -> float:
@@ -136,6 +145,8 @@ class FlatOptimizer:
             # hyper = [lr, bc1, bc2, clip, b1, b2, eps, wd]
             self.hyper = feeder(s.master.device).put(
                 "opt_hyper", [lr, bc1, bc2, self.clip_grad, self.b1, self.b2, self.eps, self.weight_decay])
+        if self.ema is not None:
+            self.ema.prepare()
 
     def launch(self) -> None:
         s = self.store
@@ -230,6 +241,8 @@ class FlatOptimizer:
             else:
                 ext.opt_sgd(s.master, s.grad, self.trace, shadow, rows, self.meta, self.hyper, self.gnorm_sq,
                             self.momentum)
+            if self.ema is not None:
+                self.ema.update_rows(rows, self.meta)
         else:
             for r0, n, _ in rows.tolist():
                 self._step_torch(*self._cur, lo=r0, hi=r0 + n)
@@ -239,6 +252,8 @@ class FlatOptimizer:
         self.count += 1
         self.store.version += 1  # shadow rewritten: transposed weight copies are stale
         self.last_lr = lr
+        if self.ema is not None:
+            self.ema.finish()
         return lr
 
     def _clip_scale_torch(self, g: torch.Tensor) -> torch.Tensor:
@@ -268,6 +283,8 @@ class FlatOptimizer:
             p.add_(torch.where(trainable & valid, upd, torch.zeros_like(upd)))
             if s.shadow is not s.master:
                 s.shadow[sl].copy_(p)
+            if self.ema is not None:
+                self.ema.update_torch(trainable & valid, sl)
             return
         p, g = s.master, s.grad
         seg_id, valid, decay, llrd, trust_m, trainable = self._elem_meta()
@@ -305,6 +322,8 @@ class FlatOptimizer:
             upd = -lr * self.trace * llrd
         upd = torch.where(trainable & valid, upd, torch.zeros_like(upd))
         p.add_(upd)
+        if self.ema is not None:  # valid: the segments' elements, under ZeRO-1 the owned ones
+            self.ema.update_torch(trainable & valid)
         if own is not None:
             for t, old in zip([t for t in (self.mu, self.nu, self.trace) if t is not None], saved):
                 t.copy_(torch.where(own, t, old))
@@ -354,6 +373,8 @@ class FlatOptimizer:
         else:
             ext.opt_sgd(s.master, s.grad, self.trace, shadow, rows, self.meta, self.hyper,
                         self.gnorm_sq, self.momentum)
+        if self.ema is not None:
+            self.ema.update_rows(rows, self.meta)
 
     # ---------------------------------------------------------------- state io
     def state_dict(self) -> dict:

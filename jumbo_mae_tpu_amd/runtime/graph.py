@@ -30,6 +30,9 @@ def _state_tensors(trainer) -> list[torch.Tensor]:
         v = getattr(trainer.opt, k, None)
         if v is not None:
             ts.append(v)
+    ema = getattr(trainer.opt, "ema", None)
+    if ema is not None:
+        ts.append(ema.ema)
     head = getattr(trainer.model, "head", None)
     for k in ("running_mean", "running_var"):
         v = getattr(head, k, None) if head is not None else None
@@ -58,7 +61,9 @@ class GraphedTrainStep:
         self.static = [tuple(t.clone() for t in mb) for mb in example_micro_batches]
         snap = None
         if restore:
-            snap = ([t.clone() for t in _state_tensors(trainer)], trainer.opt.count, trainer.opt.last_lr)
+            ema = getattr(trainer.opt, "ema", None)
+            snap = ([t.clone() for t in _state_tensors(trainer)], trainer.opt.count, trainer.opt.last_lr,
+                    ema.updates if ema is not None else 0)
         # warm up eagerly on a side stream (allocator pools, lazy weight copies, hipBLASLt plans)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -80,6 +85,8 @@ class GraphedTrainStep:
             for dst, src in zip(_state_tensors(trainer), snap[0]):
                 dst.copy_(src)
             trainer.opt.count, trainer.opt.last_lr = snap[1], snap[2]
+            if ema is not None:
+                ema.updates = snap[3]
             trainer.store.sync_shadow()
             torch.cuda.synchronize()
 

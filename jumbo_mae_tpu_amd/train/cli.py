@@ -3,7 +3,8 @@
 Reference: /root/reference/src/main_pretrain.py:97-167 and main_finetune.py:97-160 (note the
 underscore spelling of ``--image_mask_ratio`` and the seeds defaulting to ``random.randint`` at
 parse time).  Additions (all optional, defaults keep reference behaviour): ``--resume``,
-``--save-interval``, ``--mask-mode``, ``--compute-dtype``, ``--bucket-mb``, ``--device``.
+``--save-interval``, ``--mask-mode``, ``--compute-dtype``, ``--bucket-mb``, ``--device``,
+``--ema-decay`` (``main_finetune`` only).
 Flags the reference accepts but ignores (``--pooling``, ``--dec-posemb``, ``--label-mapping``,
 ``--ipaddr``, ``--hostname``; quirk Q10) are accepted and recorded.
 """
@@ -165,5 +166,17 @@ def finetune_parser() -> argparse.ArgumentParser:
         p.add_argument(f"--{s}-seed", type=int, default=random.randint(0, 1000000))
     p.add_argument("--label-mapping")
     _optim(p)
-    _extensions(p)
+    ext = _extensions(p)
+    ext.add_argument("--ema-decay", type=_ema_decay, default=0.0,
+                     help="exponential moving average of the weights with decay D (warm-up min(D, (1 + t) / (10 + t))), "
+                          "updated after every optimizer step: every evaluation also runs with the averaged weights "
+                          "(val/ema_loss, val/ema_acc1, val/ema_acc5) and the best of them is written to "
+                          "{name}-ema-best.msgpack; 0 <= D < 1, 0 = off")
     return p
+
+
+def _ema_decay(v: str) -> float:
+    d = float(v)
+    if not 0.0 <= d < 1.0:
+        raise argparse.ArgumentTypeError(f"--ema-decay {v}: expected 0 <= D < 1")
+    return d

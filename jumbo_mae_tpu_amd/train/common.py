@@ -157,14 +157,34 @@ def rank_states(rngs, model) -> list:
     return pdist.all_gather_object(mine)
 
 
-def save_last(args, model, opt, step, rngs, extra_state=None, postfix="last", per_rank=None, best=None):
+def make_ema(args, store, opt, resumed, log=print):
+    """--ema-decay D > 0: the weight average (optim/ema.py), created from the weights as they stand --
+    after the pretrained load, the broadcast and ``maybe_resume`` -- restored from the resume sidecar
+    where that carries one, and attached to the optimizer.  None with the flag off."""
+    decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
+    if decay <= 0.0:
+        return None
+    from ..optim.ema import WeightEma
+    ema = WeightEma(store, decay)
+    if resumed.get("ema") is not None:
+        ema.load_state_dict(resumed["ema"])
+        log(f"[resume] restored the weight EMA after {ema.updates} updates")
+    elif resumed.step > 0:
+        log("[resume] no weight EMA in the resume state: the average starts from the restored weights")
+    opt.attach_ema(ema)
+    return ema
+
+
+def save_last(args, model, opt, step, rngs, extra_state=None, postfix="last", per_rank=None, best=None, ema=None):
     """Rank 0: params msgpack (Flax tree) + resume sidecar, both written in the background.
 
     The sidecar holds the optimizer state, every rank's random state (``per_rank`` from
     ``rank_states``), the data position (train batches consumed per rank) and the best
-    validation metric so far."""
+    validation metric so far -- and, with ``ema`` (--ema-decay), the weight average and its update count."""
     if hasattr(opt, "gather_state"):
         opt.gather_state()  # collective: sharded optimizer moments made whole on every rank
+    if ema is not None:
+        ema.gather()  # collective: and the weight average
     if not pdist.info().is_main:
         return None
     tree = model.flax_params()
@@ -176,6 +196,8 @@ def save_last(args, model, opt, step, rngs, extra_state=None, postfix="last", pe
         state["rngs_per_rank"] = per_rank
     if best is not None:
         state["best"] = dict(best)
+    if ema is not None:
+        state["ema"] = ema.state_dict()
     if extra_state:
         state.update(extra_state)
     save_resume_state(ckpt_path(args.output_dir, args.name or "run", postfix, "state.pt"), state)
@@ -231,6 +253,8 @@ def maybe_resume(args, model, opt, rngs, log=print) -> Resumed:
     model.store.sync_shadow()
     log(f"[resume] restored step {st['step']} from {prefix}")
     out = Resumed(step=int(st["step"]), best=st.get("best", {}))
+    if st.get("ema") is not None:
+        out["ema"] = st["ema"]  # make_ema restores it
     if "data" in st and st.get("world_size", info.world_size) == info.world_size:
         out["data"] = st["data"]
     return out

@@ -7,7 +7,10 @@ Parity: /root/reference/src/main_finetune.py:37-94 and create_train_state
   * optimizers adamw | lamb | lars | sgd (momentum 0.9); peak LR = lr * B / 256 for LARS, raw lr
     otherwise; warmup-cosine from 1e-6 to 1e-6;
   * ``--pretrained-ckpt``: Flax msgpack; encoder subtree loaded into the fresh tree (Q6 fix);
-  * best checkpoint by maximum ``val/acc1``.
+  * best checkpoint by maximum ``val/acc1``;
+  * ``--ema-decay D`` (extension): a weight average follows every optimizer step (optim/ema.py); every
+    evaluation runs a second time with the averaged weights swapped in (``val/ema_*``) and the best of
+    them is written to ``{name}-ema-best.msgpack``.
 """
 
 from __future__ import annotations
@@ -16,7 +19,7 @@ import time
 
 import torch
 
-from ..ckpt.checkpoint import load_pretrained_params
+from ..ckpt.checkpoint import load_pretrained_params, save_params
 from ..config import ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.classifier import FinetuneModel
@@ -56,6 +59,24 @@ def evaluate(model, loader, rngs, device) -> dict:
     return {f"val/{k}": v / n for k, v in vals.items()}
 
 
+def evaluate_ema(model, ema, loader, rngs, device) -> dict:
+    """The validation pass with the averaged weights swapped into the store (COLLECTIVE under ZeRO-1):
+    val/ema_loss, val/ema_acc1, val/ema_acc5.  BatchNorm running statistics are the live ones.  A loader
+    iterator seeds its workers from the default generator, which this second pass must not advance."""
+    with ema.swapped(), torch.random.fork_rng(devices=[]):
+        res = evaluate(model, loader, rngs, device)
+    return {k.replace("val/", "val/ema_"): v for k, v in res.items()}
+
+
+def save_ema_best(args, model, ema) -> None:
+    """{name}-ema-best.msgpack: the ordinary Flax params tree of the averaged weights, copied to the
+    host while they are swapped in (COLLECTIVE under ZeRO-1; rank 0 writes)."""
+    with ema.swapped():
+        tree = model.flax_params() if pdist.info().is_main else None
+    if tree is not None:
+        save_params(args.output_dir, args.name or "run", tree, "ema-best")
+
+
 def main(args) -> dict:
     info = pdist.init_distributed(args.device)
     set_trace_ranges(args.trace_ranges)
@@ -81,6 +102,7 @@ def main(args) -> dict:
     run_step = StepRunner(trainer, hip_graph=args.hip_graph and device.type == "cuda" and info.world_size == 1)
     resumed = C.maybe_resume(args, model, opt, rngs, log)
     start = resumed.step
+    ema = C.make_ema(args, model.store, opt, resumed, log)
 
     def extra():
         if not model.cfg.batch_norm:
@@ -96,10 +118,18 @@ def main(args) -> dict:
                     use_wandb=False if args.log_file_only else None)
     if valid_loader is not None:  # SANITATION CHECK (main_finetune.py:53-54)
         result.update(evaluate(model, valid_loader, rngs, device))
+        if ema is not None:
+            result.update(evaluate_ema(model, ema, valid_loader, rngs, device))
+            result["val/ema_acc1/best"] = resumed.best("val/ema_acc1", 0.0)  # nothing is saved here
         logger.log(dict(result), start)
         log(f"[eval] step {start} {result}")
     meter = AverageMeter(use_latest=["learning_rate"])
     max_acc1 = resumed.best("val/acc1", 0.0)
+    max_ema_acc1 = resumed.best("val/ema_acc1", 0.0)
+
+    def best():
+        return {"val/acc1": max_acc1, **({"val/ema_acc1": max_ema_acc1} if ema is not None else {})}
+
     it = C.DevicePrefetcher(train_loader, device) if train_loader is not None else None
     t0 = time.time()
     perf = C.PerfClock(start, args.train_batch_size, finetune_fwd_flops_per_image(model.cfg), info.world_size)
@@ -130,15 +160,22 @@ def main(args) -> dict:
             if res["val/acc1"] > max_acc1:  # identical on every rank (all-reduced)
                 max_acc1 = res["val/acc1"]
                 C.save_last(args, model, opt, step, rngs, extra(), postfix="best", per_rank=per_rank,
-                            best={"val/acc1": max_acc1})
+                            best=best(), ema=ema)
+            if ema is not None:
+                res.update(evaluate_ema(model, ema, valid_loader, rngs, device))
+                if res["val/ema_acc1"] > max_ema_acc1:  # identical on every rank (all-reduced)
+                    max_ema_acc1 = res["val/ema_acc1"]
+                    save_ema_best(args, model, ema)
             if info.is_main:
                 res["val/acc1/best"] = max_acc1
+                if ema is not None:
+                    res["val/ema_acc1/best"] = max_ema_acc1
                 res["processed_samples"] = step * args.train_batch_size
                 logger.log(res, step)
                 log(f"[eval] step {step} {res}")
             result.update(res)
         if do_save:
-            C.save_last(args, model, opt, step, rngs, extra(), per_rank=per_rank, best={"val/acc1": max_acc1})
+            C.save_last(args, model, opt, step, rngs, extra(), per_rank=per_rank, best=best(), ema=ema)
         if stop:
             log(f"[train] --stop-after-steps: stopping at step {step}")
             break
