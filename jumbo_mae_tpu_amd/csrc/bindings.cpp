@@ -438,22 +438,23 @@ void opt_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor trace, c10::optiona
 }
 
 // weight EMA: flat fp32 master / ema of one length on one GPU, an int32 [nchunks, 3] chunk table
+// (what: the second buffer's name in the messages -- the norm monitor checks grad and p_old with it)
 void check_ema_pair(const torch::Tensor& master, const torch::Tensor& ema, const torch::Tensor& rows,
-                    const char* fn) {
+                    const char* fn, const char* what = "ema") {
   TORCH_CHECK(master.is_cuda() && ema.is_cuda() && rows.is_cuda() && ema.device() == master.device() &&
                   rows.device() == master.device(),
-              fn, ": master, ema and rows must be tensors on one GPU");
+              fn, ": master, ", what, " and rows must be tensors on one GPU");
   TORCH_CHECK(master.scalar_type() == torch::kFloat32 && ema.scalar_type() == torch::kFloat32, fn,
-              ": master and ema must be fp32");
+              ": master and ", what, " must be fp32");
   TORCH_CHECK(master.dim() == 1 && ema.dim() == 1 && master.is_contiguous() && ema.is_contiguous(), fn,
-              ": master and ema must be flat contiguous buffers");
-  TORCH_CHECK(ema.numel() == master.numel(), fn, ": ema has ", ema.numel(), " elements, the rows reach into master's ",
-              master.numel());
+              ": master and ", what, " must be flat contiguous buffers");
+  TORCH_CHECK(ema.numel() == master.numel(), fn, ": ", what, " has ", ema.numel(),
+              " elements, the rows reach into master's ", master.numel());
   TORCH_CHECK(rows.scalar_type() == torch::kInt32 && rows.dim() == 2 && rows.size(1) == 3 && rows.is_contiguous(), fn,
               ": rows must be a contiguous int32 [nchunks, 3] chunk table");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(ema.data_ptr()) % 16 == 0,
-              fn, ": master and ema must be 16-byte aligned");
+              fn, ": master and ", what, " must be 16-byte aligned");
 }
 
 void opt_ema(torch::Tensor master, torch::Tensor ema, torch::Tensor rows, torch::Tensor meta, torch::Tensor ema_hyper) {
@@ -480,6 +481,39 @@ void ema_swap(torch::Tensor master, torch::Tensor ema, c10::optional<torch::Tens
   }
   jm_ema_swap(master.data_ptr<float>(), ema.data_ptr<float>(), shadow_ptr(shadow), chp(rows), nch(rows),
               (long)master.numel(), stream());
+}
+
+// norm monitor: out[seg] = [sum g^2, sum p^2, sum (p - p_old)^2, max |g|, non-finite g, non-finite p,
+// elements] over the rows, fp64 [segments, 7]; every row of out is written, whatever it held
+torch::Tensor opt_seg_stats(torch::Tensor master, torch::Tensor grad, c10::optional<torch::Tensor> p_old,
+                            torch::Tensor rows, torch::Tensor meta, c10::optional<torch::Tensor> out) {
+  check_ema_pair(master, grad, rows, "opt_seg_stats", "grad");
+  const bool old = p_old.has_value() && p_old->defined();
+  if (old) check_ema_pair(master, *p_old, rows, "opt_seg_stats", "p_old");
+  TORCH_CHECK(meta.is_cuda() && meta.device() == master.device() && meta.scalar_type() == torch::kFloat32 &&
+                  meta.is_contiguous() && meta.dim() == 2 && meta.size(1) == 4 && meta.size(0) >= 1,
+              "opt_seg_stats: meta must be a contiguous fp32 [segments, 4] GPU tensor");
+  const long nseg = meta.size(0);
+  const auto f64 = master.options().dtype(torch::kFloat64);
+  torch::Tensor o;
+  if (out.has_value() && out->defined()) {
+    o = *out;
+    TORCH_CHECK(o.is_cuda() && o.device() == master.device() && o.scalar_type() == torch::kFloat64 &&
+                    o.is_contiguous() && o.dim() == 2 && o.size(0) == nseg && o.size(1) == JM_SEG_STATS_COLS,
+                "opt_seg_stats: out must be a contiguous fp64 [segments, ", JM_SEG_STATS_COLS,
+                "] tensor on master's GPU");
+  } else {
+    o = torch::empty({nseg, (long)JM_SEG_STATS_COLS}, f64);
+  }
+#ifdef JM_DEBUG
+  auto part = torch::zeros({(long)nch(rows) + 1, (long)JM_SEG_STATS_COLS}, f64);  // a skipped row adds nothing
+#else
+  auto part = torch::empty({(long)nch(rows) + 1, (long)JM_SEG_STATS_COLS}, f64);
+#endif
+  jm_opt_seg_stats(master.data_ptr<float>(), grad.data_ptr<float>(), old ? p_old->data_ptr<float>() : nullptr,
+                   chp(rows), nch(rows), meta.data_ptr<float>(), (int)nseg, (long)master.numel(),
+                   part.data_ptr<double>(), o.data_ptr<double>(), stream());
+  return o;
 }
 
 // ------------------------------------------------------------------------------ MAE
@@ -1714,6 +1748,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("opt_ema", &opt_ema, py::arg("master"), py::arg("ema"), py::arg("rows"), py::arg("meta"),
         py::arg("ema_hyper"));
   m.def("ema_swap", &ema_swap, py::arg("master"), py::arg("ema"), py::arg("shadow"), py::arg("rows"));
+  m.def("opt_seg_stats", &opt_seg_stats, py::arg("master"), py::arg("grad"), py::arg("p_old"), py::arg("rows"),
+        py::arg("meta"), py::arg("out") = py::none());
   m.def("patchify_normalize", &patchify_normalize);
   m.def("gather_patches", &gather_patches);
   m.def("embed_finish", &embed_finish);

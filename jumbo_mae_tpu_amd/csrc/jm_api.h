@@ -202,6 +202,14 @@ void jm_opt_ema(const float* p, float* ema, const int* chunks, int nchunks, cons
                 const float* ema_hyper, long n, hipStream_t st);
 // exchange p and ema on every row, bit for bit (+ the bf16 shadow copy of the new p) (ema_swap_kernel)
 void jm_ema_swap(float* p, float* ema, uint16_t* shadow, const int* chunks, int nchunks, long n, hipStream_t st);
+// norm monitor (optim/monitor.py): out[seg] = [sum g^2, sum p^2, sum (p - p_old)^2, max |g|, non-finite g,
+// non-finite p, covered elements] over the rows of each segment, in fp64; non-finite values are counted and
+// left out of the sums, frozen segments (meta[seg][3] == 0) report p only, p_old may be null (column 2 = 0).
+// part: fp64 [nchunks, 7] chunk partials; out: fp64 [nseg, 7], every row written (no rows: zeros); n =
+// elements of p, g and p_old (seg_stats_kernel, seg_stats_finish_kernel)
+constexpr int JM_SEG_STATS_COLS = 7;
+void jm_opt_seg_stats(const float* p, const float* g, const float* p_old, const int* chunks, int nchunks,
+                      const float* meta, int nseg, long n, double* part, double* out, hipStream_t st);
 int jm_debug_line_optim();
 
 // ---- mae.hip

@@ -323,6 +323,162 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(uint32_t* __restrict__ p,
   }
 }
 
+// Norm monitor (optim/monitor.py): per-segment statistics of p (the master), g and the step p - p_old
+// over the rows of a chunk table, all in fp64 -- every fp32 value is widened before it is squared or
+// subtracted, so 2^100 does not overflow and a subnormal's square is not lost.  Finiteness is read
+// from the exponent bits; a non-finite value is counted and adds nothing to any sum.  Columns of a
+// row of part / out: [sum g^2, sum p^2, sum (p - p_old)^2, max |g|, non-finite g, non-finite p,
+// elements].
+constexpr int NS = JM_SEG_STATS_COLS;
+
+JM_DEVICE bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+struct SegAcc {
+  double g2, p2, d2;
+  float gmax;
+  int gbad, pbad;
+};
+
+// one element; LIVE = false (frozen segment): p only, OLD = false: no snapshot
+template <bool LIVE, bool OLD>
+JM_DEVICE void seg_acc(SegAcc& a, float pv, float gv, float ov) {
+  const bool pf = finite_bits(pv);
+  const double pd = pf ? (double)pv : 0.0;
+  a.p2 = __builtin_fma(pd, pd, a.p2);
+  a.pbad += pf ? 0 : 1;
+  if (LIVE) {
+    const bool gf = finite_bits(gv);
+    const double gd = gf ? (double)gv : 0.0;
+    a.g2 = __builtin_fma(gd, gd, a.g2);
+    a.gmax = fmaxf(a.gmax, gf ? fabsf(gv) : 0.f);
+    a.gbad += gf ? 0 : 1;
+    if (OLD) {
+      const double d = (pf && finite_bits(ov)) ? pd - (double)ov : 0.0;
+      a.d2 = __builtin_fma(d, d, a.d2);
+    }
+  }
+}
+
+// one row; the access pattern of ema_kernel: 16 B per lane, the last len % 4 elements one by one
+template <bool LIVE, bool OLD>
+JM_DEVICE void seg_row(SegAcc& a, const float* __restrict__ p, const float* __restrict__ g,
+                       const float* __restrict__ o, const Chunk c) {
+  const int n4 = c.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const long k = (long)c.start + 4L * i;
+    float pv[4], gv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4] = {0.f, 0.f, 0.f, 0.f};
+    load4(p + k, pv);
+    if (LIVE) load4(g + k, gv);
+    if (LIVE && OLD) load4(o + k, ov);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) seg_acc<LIVE, OLD>(a, pv[j], gv[j], ov[j]);
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < c.len; i += 256) {
+    const long k = (long)c.start + i;
+    seg_acc<LIVE, OLD>(a, p[k], LIVE ? g[k] : 0.f, (LIVE && OLD) ? o[k] : 0.f);
+  }
+}
+
+// 64-lane butterflies: the same pairs in the same order on every run
+JM_DEVICE double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
+  return v;
+}
+
+// One workgroup per chunk-table row: part[row] = the row's 7 partials.  Frozen segments
+// (meta[seg][3] == 0): g and p_old are not read, columns 0, 2, 3, 4 are 0.  n = elements of p, g and
+// p_old, nseg = rows of meta (debug build: a row outside them is recorded and skipped; its partials
+// stay the zeros the debug binding allocates).
+template <bool OLD>
+__global__ __launch_bounds__(256) void seg_stats_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                        const float* __restrict__ p_old,
+                                                        const Chunk* __restrict__ chunks,
+                                                        const float* __restrict__ meta, long n, int nseg,
+                                                        double* __restrict__ part) {
+  __shared__ double sh[4][NS];
+  const Chunk c = chunks[blockIdx.x];
+  JM_DGUARD(c.start >= 0 && c.len >= 0 && (long)c.start + c.len <= n && (c.start & 3) == 0 && c.seg >= 0 &&
+            c.seg < nseg);
+  SegAcc a = {0.0, 0.0, 0.0, 0.f, 0, 0};
+  if (meta[4 * c.seg + 3] == 0.f) {  // block-uniform
+    seg_row<false, false>(a, p, g, p_old, c);
+  } else {
+    seg_row<true, OLD>(a, p, g, p_old, c);
+  }
+  double v[NS - 1] = {a.g2, a.p2, a.d2, (double)a.gmax, (double)a.gbad, (double)a.pbad};
+#pragma unroll
+  for (int k = 0; k < NS - 1; ++k) {
+    if (k == 3) {
+      v[k] = (double)wave_max((float)v[k]);
+    } else {
+      v[k] = wave_sum_f64(v[k]);
+    }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < NS - 1; ++k) sh[wave][k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* out = part + (long)blockIdx.x * NS;
+#pragma unroll
+    for (int k = 0; k < NS - 1; ++k) {
+      out[k] = k == 3 ? fmax(fmax(sh[0][k], sh[1][k]), fmax(sh[2][k], sh[3][k]))
+                      : (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
+    }
+    out[NS - 1] = (double)c.len;
+  }
+}
+
+// One workgroup per segment: out[seg] = the partials of the segment's rows combined in chunk order
+// (thread-strided, then a fixed tree); a segment without rows gets zeros.  Rows are sorted by segment
+// (chunk_sums_kernel's precondition), so the run is found by bisection.  Writes, never adds: out
+// needs no initialisation.
+__global__ __launch_bounds__(256) void seg_stats_finish_kernel(const Chunk* __restrict__ chunks, int nchunks,
+                                                               const double* __restrict__ part,
+                                                               double* __restrict__ out) {
+  __shared__ double red[NS][256];
+  const int seg = blockIdx.x;
+  int lo = 0, hi = nchunks;
+  while (lo < hi) {  // first row with segment >= seg
+    const int m = (lo + hi) >> 1;
+    if (chunks[m].seg < seg) lo = m + 1; else hi = m;
+  }
+  int end = lo;
+  hi = nchunks;
+  while (end < hi) {  // first row with segment > seg
+    const int m = (end + hi) >> 1;
+    if (chunks[m].seg <= seg) end = m + 1; else hi = m;
+  }
+  double a[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) a[k] = 0.0;
+  for (int j = lo + threadIdx.x; j < end; j += 256) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const double x = part[(long)j * NS + k];
+      a[k] = k == 3 ? fmax(a[k], x) : a[k] + x;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NS; ++k) red[k][threadIdx.x] = a[k];
+  __syncthreads();
+#pragma unroll
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const double x = red[k][threadIdx.x + h];
+        red[k][threadIdx.x] = k == 3 ? fmax(red[k][threadIdx.x], x) : red[k][threadIdx.x] + x;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < NS) out[(long)seg * NS + threadIdx.x] = red[threadIdx.x][0];
+}
+
 }  // namespace
 
 // cpart: nchunks (sumsq) / 2 * nchunks (LAMB / LARS norms) floats of chunk partials
@@ -374,6 +530,19 @@ void jm_ema_swap(float* p, float* ema, uint16_t* shadow, const int* chunks, int 
   if (nchunks < 1) return;
   ema_swap_kernel<<<nchunks, 256, 0, st>>>(reinterpret_cast<uint32_t*>(p), reinterpret_cast<uint32_t*>(ema), shadow,
                                            (const Chunk*)chunks, n);
+}
+
+void jm_opt_seg_stats(const float* p, const float* g, const float* p_old, const int* chunks, int nchunks,
+                      const float* meta, int nseg, long n, double* part, double* out, hipStream_t st) {
+  if (nseg < 1) return;
+  if (nchunks > 0) {
+    if (p_old) {
+      seg_stats_kernel<true><<<nchunks, 256, 0, st>>>(p, g, p_old, (const Chunk*)chunks, meta, n, nseg, part);
+    } else {
+      seg_stats_kernel<false><<<nchunks, 256, 0, st>>>(p, g, nullptr, (const Chunk*)chunks, meta, n, nseg, part);
+    }
+  }
+  seg_stats_finish_kernel<<<nseg, 256, 0, st>>>((const Chunk*)chunks, nchunks, part, out);
 }
 
 JM_DEBUG_EXPORT(optim)

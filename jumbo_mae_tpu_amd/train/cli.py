@@ -4,7 +4,7 @@ Reference: /root/reference/src/main_pretrain.py:97-167 and main_finetune.py:97-1
 underscore spelling of ``--image_mask_ratio`` and the seeds defaulting to ``random.randint`` at
 parse time).  Additions (all optional, defaults keep reference behaviour): ``--resume``,
 ``--save-interval``, ``--mask-mode``, ``--compute-dtype``, ``--bucket-mb``, ``--device``,
-``--ema-decay`` (``main_finetune`` only).
+``--log-norms``, ``--ema-decay`` (``main_finetune`` only).
 Flags the reference accepts but ignores (``--pooling``, ``--dec-posemb``, ``--label-mapping``,
 ``--ipaddr``, ``--hostname``; quirk Q10) are accepted and recorded.
 """
@@ -120,6 +120,13 @@ def _extensions(p: argparse.ArgumentParser):
     g.add_argument("--skip-nonfinite", action="store_true",
                    help="skip the update of a step whose loss is non-finite (one host sync per step); "
                         "default: abort at the next log step")
+    g.add_argument("--log-norms", default="off", choices=["off", "global", "layer"],
+                   help="at every logged step, for that step itself: gradient / weight / update norms from one fused "
+                        "fp64 pass over the optimizer's chunk table (optim/monitor.py).  global: train/grad_norm, "
+                        "train/param_norm, train/update_norm, train/update_ratio, train/grad_absmax, "
+                        "train/nonfinite_grads, train/nonfinite_params (and train/clip_scale with --clip-grad); "
+                        "layer: also norms/grad/<group>, norms/param/<group>, norms/update_ratio/<group> per "
+                        "layer group.  Non-finite values are counted per leaf and the leaves named before the abort")
     return g
 
 

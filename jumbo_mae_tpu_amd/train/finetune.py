@@ -10,7 +10,9 @@ Parity: /root/reference/src/main_finetune.py:37-94 and create_train_state
   * best checkpoint by maximum ``val/acc1``;
   * ``--ema-decay D`` (extension): a weight average follows every optimizer step (optim/ema.py); every
     evaluation runs a second time with the averaged weights swapped in (``val/ema_*``) and the best of
-    them is written to ``{name}-ema-best.msgpack``.
+    them is written to ``{name}-ema-best.msgpack``;
+  * ``--log-norms global|layer`` (extension): gradient / weight / update norms of every logged step
+    (optim/monitor.py), written before the non-finite check so that an abort names its leaves.
 """
 
 from __future__ import annotations
@@ -23,6 +25,7 @@ from ..ckpt.checkpoint import load_pretrained_params, save_params
 from ..config import ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.classifier import FinetuneModel
+from ..optim.monitor import log_norms, make_monitor
 from ..parallel import dist as pdist
 from ..utils.flops import finetune_fwd_flops_per_image
 from ..utils.mixup import Mixup
@@ -103,6 +106,7 @@ def main(args) -> dict:
     resumed = C.maybe_resume(args, model, opt, rngs, log)
     start = resumed.step
     ema = C.make_ema(args, model.store, opt, resumed, log)
+    monitor = make_monitor(args, opt)  # --log-norms
 
     def extra():
         if not model.cfg.batch_norm:
@@ -136,15 +140,20 @@ def main(args) -> dict:
     step = start
     for step in range(start + 1, args.training_steps + 1):
         micro = [tuple(next(it)) for _ in range(args.grad_accum)]
+        log_step = args.log_interval > 0 and step % args.log_interval == 0
+        if monitor is not None and log_step:
+            monitor.begin()  # the weights this step starts from
         metrics = run_step(micro)
         meter.update(**metrics)
-        if args.log_interval > 0 and step % args.log_interval == 0:
+        if log_step:
             summ = meter.summary("train/")
             summ["processed_samples"] = step * args.train_batch_size
             summ.update(perf.summary(step))
             comm = trainer.comm_ms()
             if comm is not None:
                 summ["perf/comm_ms"] = comm
+            if monitor is not None:  # this step's own values, not a mean over the interval
+                log_norms(monitor, summ, log)
             C.check_finite(summ, step)
             if info.is_main:
                 logger.log(summ, step)

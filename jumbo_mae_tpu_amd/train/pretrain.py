@@ -8,7 +8,9 @@ Parity: /root/reference/src/main_pretrain.py:37-94 and create_train_state
     train/learning_rate, processed_samples, val/loss, val/loss/best;
   * at eval_interval (and the last step): evaluates, saves ``{name}-best.msgpack`` on a new minimum
     validation loss and ``{name}-last.msgpack`` (the reference writes "last" before the evaluation;
-    here it follows it so that its resume sidecar carries the updated best metric).
+    here it follows it so that its resume sidecar carries the updated best metric);
+  * ``--log-norms global|layer`` (extension): gradient / weight / update norms of every logged step
+    (optim/monitor.py), written before the non-finite check so that an abort names its leaves.
 Launch: ``torchrun --nproc-per-node 8 src/main_pretrain.py <reference flags>``.
 """
 
@@ -22,6 +24,7 @@ from ..config import DecoderConfig, ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.mae import PretrainModel
 from ..ops import knn as knn_ops
+from ..optim.monitor import log_norms, make_monitor
 from ..parallel import dist as pdist
 from ..utils.flops import pretrain_fwd_flops_per_image
 from ..utils.rng import RngStreams
@@ -177,6 +180,7 @@ def main(args) -> dict:
     run_step = StepRunner(trainer, hip_graph=args.hip_graph and device.type == "cuda" and info.world_size == 1)
     resumed = C.maybe_resume(args, model, opt, rngs, log)
     start = resumed.step
+    monitor = make_monitor(args, opt)  # --log-norms
 
     # a resumed run continues the data stream after the batches the interrupted run consumed
     train_loader, valid_loader = create_dataloaders(args, info.rank, info.world_size, resumed.batches,
@@ -203,15 +207,20 @@ def main(args) -> dict:
         for _ in range(args.grad_accum):
             b = next(it)
             micro.append((b[0] if isinstance(b, (list, tuple)) else b,))
+        log_step = args.log_interval > 0 and step % args.log_interval == 0
+        if monitor is not None and log_step:
+            monitor.begin()  # the weights this step starts from
         metrics = run_step(micro)
         meter.update(**metrics)
-        if args.log_interval > 0 and step % args.log_interval == 0:
+        if log_step:
             summ = meter.summary("train/")
             summ["processed_samples"] = step * args.train_batch_size
             summ.update(perf.summary(step))
             comm = trainer.comm_ms()
             if comm is not None:
                 summ["perf/comm_ms"] = comm
+            if monitor is not None:  # this step's own values, not a mean over the interval
+                log_norms(monitor, summ, log)
             C.check_finite(summ, step)
             if info.is_main:
                 logger.log(summ, step)
