@@ -1641,6 +1641,40 @@ std::vector<torch::Tensor> knn_vote(torch::Tensor idx, torch::Tensor sim, torch:
   return {pred, hit1, hit5};
 }
 
+// attention monitor: fp64 [H, 6] = per head [sum entropy, sum max prob, sum CLS mass, max logit, bad rows, B S]
+// of softmax(q k^T / sqrt(hd)); rows_out (fp32 [B, H, S, 4], optional) receives every row's four values
+torch::Tensor attn_stats(torch::Tensor qkv, int64_t heads, int64_t n_cls, c10::optional<torch::Tensor> rows_out) {
+  TORCH_CHECK(qkv.is_cuda(), "attn_stats: qkv must be a GPU tensor");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 && qkv.is_contiguous(), "attn_stats: qkv must be contiguous bf16");
+  check_attn_shape(qkv, heads, "attn_stats");
+  const int64_t B = qkv.size(0), S = qkv.size(1), hd = qkv.size(2) / 3 / heads;
+  TORCH_CHECK(B >= 1 && S >= 1 && B < INT_MAX && S < INT_MAX && heads < INT_MAX, "attn_stats: empty or oversized qkv");
+  TORCH_CHECK(n_cls >= 0 && n_cls <= S, "attn_stats: n_cls must be in 0..S (got ", n_cls, ", S = ", S, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "attn_stats: qkv must be 16-byte aligned");
+  float* rp = nullptr;
+  if (rows_out.has_value() && rows_out->defined()) {
+    const auto& r = *rows_out;
+    TORCH_CHECK(r.is_cuda() && r.device() == qkv.device() && r.scalar_type() == torch::kFloat32 && r.is_contiguous() &&
+                    r.dim() == 4 && r.size(0) == B && r.size(1) == heads && r.size(2) == S && r.size(3) == 4,
+                "attn_stats: rows_out must be a contiguous fp32 [B, H, S, 4] tensor on qkv's GPU");
+    rp = r.data_ptr<float>();
+  }
+  const auto f64 = qkv.options().dtype(torch::kFloat64);
+  const long np = jm_attn_stats_part((int)B, (int)S, (int)heads);
+#ifdef JM_DEBUG
+  auto part = torch::zeros({np}, f64);  // a workgroup stopped by its guard adds nothing
+#else
+  auto part = torch::empty({np}, f64);
+#endif
+  auto out = torch::empty({heads, (long)JM_ATTN_STATS_COLS}, f64);
+  check_rc(jm_attn_stats(qkv.data_ptr(), (int)B, (int)S, (int)heads, (int)hd, (int)n_cls, part.data_ptr<double>(), rp,
+                         stream()),
+           "attn_stats");
+  check_rc(jm_attn_stats_finish(part.data_ptr<double>(), (int)B, (int)S, (int)heads, out.data_ptr<double>(), stream()),
+           "attn_stats (finish)");
+  return out;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1651,7 +1685,8 @@ py::dict debug_lines() {
       {"gemm", jm_debug_line_gemm},           {"gemm_tn", jm_debug_line_gemm_tn},
       {"layernorm", jm_debug_line_layernorm}, {"loss", jm_debug_line_loss},
       {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
-      {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn}};
+      {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
+      {"attn_stats", jm_debug_line_attn_stats}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1786,6 +1821,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n"), py::arg("out") = py::none());
   m.def("bn_chunk_rows", &jm_bn_chunk_rows, "rows per workgroup of the BatchNorm kernels");
   m.def("bn_block_cols", &jm_bn_block_cols, "columns per workgroup of the BatchNorm kernels");
+  m.def("attn_stats", &attn_stats, py::arg("qkv"), py::arg("heads"), py::arg("n_cls"),
+        py::arg("rows_out") = py::none(), "per-head attention statistics, fp64 [H, 6]");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

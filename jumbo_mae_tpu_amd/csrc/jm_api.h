@@ -383,3 +383,18 @@ int jm_knn_topk(const void* q, long ldq, const void* bank, long ldb, const int* 
 int jm_knn_vote(const int* idx, const float* sim, const int* bank_labels, const int* labels, double T, int Nq, int Nb,
                 int k, int* pred, uint8_t* hit1, uint8_t* hit5, hipStream_t st);
 int jm_debug_line_knn();
+
+// ---- attn_stats.hip (qkv: bf16 [B, S, 3, H, hd] contiguous, 16-byte aligned, hd one of jm_attn_head_dims;
+// 0 <= n_cls <= S; -1 bad argument or a batch element of 2 GiB or more, -2 failed launch)
+// columns of the per-head table: sums of the rows' entropy / largest probability / CLS mass over the good rows
+// (finite entropy), the largest logit of the good rows (-inf: none), the rows that are not good, B S
+constexpr int JM_ATTN_STATS_COLS = 6;
+// doubles of the workspace part
+long jm_attn_stats_part(int B, int S, int H);
+// part = per workgroup partials; rows_out (fp32 [B, H, S, 4] or null) = (entropy, largest probability, CLS mass,
+// largest logit) of every row
+int jm_attn_stats(const void* qkv, int B, int S, int H, int hd, int n_cls, double* part, float* rows_out,
+                  hipStream_t st);
+// out (fp64 [H, 6]) = the partials added per head in (b, tile) order with a fixed tree
+int jm_attn_stats_finish(const double* part, int B, int S, int H, double* out, hipStream_t st);
+int jm_debug_line_attn_stats();

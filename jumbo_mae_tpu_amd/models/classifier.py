@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from ..config import ViTConfig
+from ..ops import attn_stats as AS
 from ..ops import functional as Fn
 from ..ops import mae as mae_ops
 from ..ops import prims as P
@@ -162,6 +163,15 @@ class FinetuneModel:
         top = logits.topk(k, -1).indices
         accs = torch.gather(lab, 1, top)
         return accs[:, 0], accs.any(-1)
+
+    @torch.no_grad()
+    def attention_stats(self, images_u8) -> dict:
+        """``{layer_<i>: float64 [H, 6]}`` (ops/attn_stats.py) of every encoder layer in one ``det=True``
+        forward of the unmixed images; the head does not run, so BatchNorm statistics are untouched."""
+        rows, _ = self.patches(images_u8, None, None, True, plan=None)
+        names = [f"layer_{i}" for i in range(len(self.encoder.layers))]
+        return AS.collect_layers(names, lambda: self.features(rows, images_u8.shape[0], None, True),
+                                 self.cfg.num_cls_tokens)
 
     @torch.no_grad()
     def evaluate(self, images_u8, labels, rngs=None) -> dict:

@@ -19,6 +19,7 @@ import torch
 
 from ..config import DecoderConfig, ViTConfig
 from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
+from ..ops import attn_stats as AS
 from ..ops import mae as mae_ops
 from ..utils.mae import masking_ids
 from .params import ParamStore, trunc_normal_
@@ -126,6 +127,17 @@ class PretrainModel:
         same parameters, bit for bit: both call ``cls_features``).  Touches no random stream."""
         rows = mae_ops.mixed_patches(images_u8, None, self.cfg.patch_size, self.store.compute_dtype)
         return cls_features(self.encoder, rows, images_u8.shape[0], None, True)
+
+    @torch.no_grad()
+    def attention_stats(self, images_u8: torch.Tensor, noise: torch.Tensor | None = None) -> dict:
+        """``{name: float64 [H, 6]}`` (ops/attn_stats.py) of every attention layer in one masked
+        ``det=True`` forward: ``layer_<i>`` for the encoder (on the kept patches), ``decoder/dec_layer_<i>``
+        for the decoder -- the group names of ``optim/monitor.py group_name``.  ``noise`` as in
+        ``reconstruct``; touches no stream of the training ``rngs``."""
+        names = [f"layer_{i}" for i in range(len(self.encoder.layers))] + \
+                [f"decoder/dec_layer_{i}" for i in range(len(self.decoder.layers))]
+        return AS.collect_layers(names, lambda: self._predict(images_u8, {}, True, True, noise),
+                                 self.cfg.num_cls_tokens)
 
     @torch.no_grad()
     def evaluate(self, images_u8: torch.Tensor, valid: torch.Tensor | None = None, rngs: dict | None = None) -> dict:

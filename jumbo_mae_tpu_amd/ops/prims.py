@@ -159,6 +159,7 @@ _CLS_LOSS_OURS = True  # classification loss / accuracies on the fused kernels (
 _BN_OURS = True  # linear-probe BatchNorm on the fused kernels (csrc/batchnorm.hip), else the torch composition
 _KNN_OURS = True  # k-NN monitor's top-k and vote on the fused kernels (csrc/knn.hip), else the torch composition
 _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc/optim.hip seg_stats), else the torch composition
+_ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused kernel (csrc/attn_stats.hip), else the torch composition
 
 
 NARROW_MAX_M = 4096  # csrc/gemm.hip NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles

@@ -127,6 +127,13 @@ def _extensions(p: argparse.ArgumentParser):
                         "train/nonfinite_grads, train/nonfinite_params (and train/clip_scale with --clip-grad); "
                         "layer: also norms/grad/<group>, norms/param/<group>, norms/update_ratio/<group> per "
                         "layer group.  Non-finite values are counted per leaf and the leaves named before the abort")
+    g.add_argument("--attn-stats", type=int, default=0,
+                   help="at every evaluation rank 0 runs the first N validation images through the model once more "
+                        "(pretraining: masked by a private generator seeded with --noise-seed) and logs, per layer, "
+                        "attn/entropy/<layer> (mean row entropy of the attention softmax in nats, averaged over the "
+                        "heads; uniform attention = log S), attn/entropy_min/<layer> (the lowest head), "
+                        "attn/max_logit/<layer>, attn/max_prob/<layer>, attn/cls_mass/<layer>, and over the layers "
+                        "val/attn_entropy_min and val/attn_max_logit (ops/attn_stats.py); 0 = off")
     return g
 
 

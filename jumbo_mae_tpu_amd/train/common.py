@@ -293,3 +293,41 @@ class PerfClock:
         self.t, self.step = now, step
         return {"perf/images_per_sec": ips, "perf/step_ms": 1e3 * dt / n,
                 "perf/mfu": mfu(ips, self.flops, self.world)}
+
+
+def first_images(loader, n: int, device) -> torch.Tensor:
+    """The first ``n`` real (unpadded) images of a validation loader, uint8 [<= n, 3, S, S]."""
+    got, have = [], 0
+    for batch in DevicePrefetcher(loader, device):
+        images, labels = batch if isinstance(batch, (list, tuple)) else (batch, None)
+        if labels is not None:
+            images = images[labels != -1]
+        got.append(images[:n - have])
+        have += got[-1].shape[0]
+        if have >= n:
+            break
+    return torch.cat(got)
+
+
+def evaluate_attn_stats(model, loader, args, device, log) -> dict:
+    """--attn-stats (rank 0 only, no collectives): the attention monitor's probe pass on the first N
+    validation images -- for a model that masks (``mask_mode``) under a mask drawn from a private
+    generator seeded with --noise-seed, the same patches at every evaluation.  Nothing is taken from
+    the training streams.  Returns the ``attn/...`` and ``val/attn_...`` log values
+    (ops/attn_stats.py summarize) and prints one line per head with rows of no finite entropy."""
+    from ..ops import attn_stats as AS
+
+    with torch.random.fork_rng(devices=[]):  # a loader iterator seeds its workers from the default generator
+        images = first_images(loader, args.attn_stats, device)
+    if hasattr(model, "mask_mode"):
+        B, n = images.shape[0], model.cfg.seq_patches
+        g = torch.Generator().manual_seed(args.noise_seed)
+        noise = torch.rand((n,) if model.mask_mode == "shared" else (B, n), generator=g).to(device)
+        tables = model.attention_stats(images, noise=noise)
+    else:
+        tables = model.attention_stats(images)
+    vals, lines = AS.summarize(tables)
+    for line in lines:
+        log("[eval] " + line)
+    return vals
+

@@ -12,7 +12,9 @@ Parity: /root/reference/src/main_finetune.py:37-94 and create_train_state
     evaluation runs a second time with the averaged weights swapped in (``val/ema_*``) and the best of
     them is written to ``{name}-ema-best.msgpack``;
   * ``--log-norms global|layer`` (extension): gradient / weight / update norms of every logged step
-    (optim/monitor.py), written before the non-finite check so that an abort names its leaves.
+    (optim/monitor.py), written before the non-finite check so that an abort names its leaves;
+  * ``--attn-stats N`` (extension): at every evaluation rank 0 logs the per-layer attention entropy,
+    largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py).
 """
 
 from __future__ import annotations
@@ -125,6 +127,8 @@ def main(args) -> dict:
         if ema is not None:
             result.update(evaluate_ema(model, ema, valid_loader, rngs, device))
             result["val/ema_acc1/best"] = resumed.best("val/ema_acc1", 0.0)  # nothing is saved here
+        if args.attn_stats > 0 and info.is_main:
+            result.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
         logger.log(dict(result), start)
         log(f"[eval] step {start} {result}")
     meter = AverageMeter(use_latest=["learning_rate"])
@@ -176,6 +180,8 @@ def main(args) -> dict:
                     max_ema_acc1 = res["val/ema_acc1"]
                     save_ema_best(args, model, ema)
             if info.is_main:
+                if args.attn_stats > 0:
+                    res.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
                 res["val/acc1/best"] = max_acc1
                 if ema is not None:
                     res["val/ema_acc1/best"] = max_ema_acc1

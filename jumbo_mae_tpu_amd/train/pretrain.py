@@ -10,7 +10,9 @@ Parity: /root/reference/src/main_pretrain.py:37-94 and create_train_state
     validation loss and ``{name}-last.msgpack`` (the reference writes "last" before the evaluation;
     here it follows it so that its resume sidecar carries the updated best metric);
   * ``--log-norms global|layer`` (extension): gradient / weight / update norms of every logged step
-    (optim/monitor.py), written before the non-finite check so that an abort names its leaves.
+    (optim/monitor.py), written before the non-finite check so that an abort names its leaves;
+  * ``--attn-stats N`` (extension): at every evaluation rank 0 logs the per-layer attention entropy,
+    largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py).
 Launch: ``torchrun --nproc-per-node 8 src/main_pretrain.py <reference flags>``.
 """
 
@@ -110,18 +112,7 @@ def knn_metrics(feats: torch.Tensor, labels: torch.Tensor, k: int, T: float) -> 
     return {"val/knn_acc1": h1 / max(cnt, 1.0), "val/knn_acc5": h5 / max(cnt, 1.0)}
 
 
-def first_images(loader, n: int, device) -> torch.Tensor:
-    """The first ``n`` real (unpadded) images of a validation loader, uint8 [<= n, 3, S, S]."""
-    got, have = [], 0
-    for batch in C.DevicePrefetcher(loader, device):
-        images, labels = batch if isinstance(batch, (list, tuple)) else (batch, None)
-        if labels is not None:
-            images = images[labels != -1]
-        got.append(images[:n - have])
-        have += got[-1].shape[0]
-        if have >= n:
-            break
-    return torch.cat(got)
+first_images = C.first_images
 
 
 def recon_panel(images_u8: torch.Tensor, out: dict):
@@ -193,6 +184,8 @@ def main(args) -> dict:
         result.update(evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log))
         if args.recon_images > 0 and info.is_main:
             result.update(evaluate_recon(model, valid_loader, args, device, start, log))
+        if args.attn_stats > 0 and info.is_main:
+            result.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
         logger.log(dict(result), start)
         log(f"[eval] step {start} {result}")
     meter = AverageMeter(use_latest=["learning_rate"])
@@ -240,6 +233,8 @@ def main(args) -> dict:
             if info.is_main:
                 if args.recon_images > 0:
                     res.update(evaluate_recon(model, valid_loader, args, device, step, log))
+                if args.attn_stats > 0:
+                    res.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
                 res["val/loss/best"] = min_val_loss
                 res["processed_samples"] = step * args.train_batch_size
                 logger.log(res, step)
