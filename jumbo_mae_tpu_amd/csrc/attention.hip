@@ -1154,35 +1154,43 @@ __global__ __launch_bounds__(64 * NWV, 2) void attn_bwd3_kernel(const uint16_t* 
   }
 }
 
+// ---------------------------------------------------------------------------- host launchers
+// raises kernel FN's dynamic-LDS limit past the 64 KiB default, once per instantiation
+template <auto FN>
+void lds_limit(size_t bytes) {
+  static bool done = false;
+  if (bytes > 64 * 1024 && !done) {
+    (void)hipFuncSetAttribute((const void*)FN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done = true;
+  }
+}
+
+// calls f with the forward's EX = S > SP - 32 as a compile-time bool (true for every S that
+// dispatch_sp sends to SP 32 or 64)
+template <int SP, class F>
+int with_ex(int S, F&& f) {
+  if constexpr (SP > 64) {
+    if (S <= SP - 32) return f(std::false_type{});
+  }
+  return f(std::true_type{});
+}
+
 // forward images: row-major K and V, XOR-swizzled (V^T operands through ds_read_b64_tr_b16)
 template <int HD, int SP>
-size_t fwd_smem() { return (size_t)(2 * SP * HD) * 2; }
+constexpr size_t fwd_smem() { return (size_t)(2 * SP * HD) * 2; }
 
 // one (b, h) per workgroup (S > 64; the short encoder sequences take the multi-pair kernel)
 template <int HD, int SP, bool DROP>
 int run_fwd(const uint16_t* qkv, uint16_t* out, float* lse_out, int B, int S, int H, float scale, AttnDrop dr,
             hipStream_t st) {
-  dim3 grid(B * H);
-  const size_t sm = fwd_smem<HD, SP>();
-  if (sm > 160 * 1024) return -3;
-  if (S > SP - 32) {
-    static bool attr_ex = false;
-    if (sm > 64 * 1024 && !attr_ex) {
-      (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<HD, SP, true, DROP>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-      attr_ex = true;
-    }
-    attn_fwd_kernel<HD, SP, true, DROP><<<grid, 256, sm, st>>>(qkv, out, lse_out, S, H, scale, dr);
-  } else {
-    static bool attr = false;
-    if (sm > 64 * 1024 && !attr) {
-      (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<HD, SP, false, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sm);
-      attr = true;
-    }
-    attn_fwd_kernel<HD, SP, false, DROP><<<grid, 256, sm, st>>>(qkv, out, lse_out, S, H, scale, dr);
-  }
-  return 0;
+  constexpr size_t sm = fwd_smem<HD, SP>();
+  static_assert(sm <= 160 * 1024, "forward LDS");
+  return with_ex<SP>(S, [&](auto ex) {
+    constexpr bool EX = decltype(ex)::value;
+    lds_limit<attn_fwd_kernel<HD, SP, EX, DROP>>(sm);
+    attn_fwd_kernel<HD, SP, EX, DROP><<<dim3(B * H), 256, sm, st>>>(qkv, out, lse_out, S, H, scale, dr);
+    return 0;
+  });
 }
 
 // The backward kernel per shape -- the single source of that choice for run_bwd and
@@ -1202,30 +1210,16 @@ int run_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const fl
   if constexpr (HD == 64 && SP > 64) {
     constexpr size_t sm8 = bwd2_smem<HD, SP, 128>();
     static_assert(sm8 <= 160 * 1024, "8-wave backward LDS");
-    static bool attr8 = false;
-    if (!attr8) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd3_kernel<HD, SP, 8, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sm8);
-      attr8 = true;
-    }
+    lds_limit<attn_bwd3_kernel<HD, SP, 8, DROP>>(sm8);
     attn_bwd3_kernel<HD, SP, 8, DROP><<<dim3(B * H), 512, sm8, st>>>(qkv, o, dO, lse_in, out, S, H, scale, dbias_part, dr);
   } else {
     constexpr size_t sm = bwd2_smem<HD, SP>();
     static_assert(sm <= 160 * 1024, "backward LDS");
-    static bool attr = false;
     if constexpr (HD == 32) {
-      if (sm > 64 * 1024 && !attr) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd3_kernel<HD, SP, 4, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)sm);
-        attr = true;
-      }
+      lds_limit<attn_bwd3_kernel<HD, SP, 4, DROP>>(sm);
       attn_bwd3_kernel<HD, SP, 4, DROP><<<dim3(B * H), 256, sm, st>>>(qkv, o, dO, lse_in, out, S, H, scale, dbias_part, dr);
     } else {
-      if (sm > 64 * 1024 && !attr) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel<HD, SP, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)sm);
-        attr = true;
-      }
+      lds_limit<attn_bwd2_kernel<HD, SP, DROP>>(sm);
       attn_bwd2_kernel<HD, SP, DROP><<<dim3(((B + BWD2_PPW - 1) / BWD2_PPW) * H), 256, sm, st>>>(
           qkv, o, dO, lse_in, out, S, H, scale, dbias_part, B, BWD2_PPW, dr);
     }
@@ -1242,34 +1236,33 @@ constexpr int FWD_ML_PAIRS = 4;
 template <int HD, int SP, bool DROP>
 int run_fwd_ml(const uint16_t* qkv, uint16_t* out, float* lse_out, int B, int S, int H, float scale, AttnDrop dr,
                hipStream_t st) {
-  const size_t sm = fwd_smem<HD, SP>();
-  static bool attr_set[2] = {false, false};
-  const bool ex = S > SP - 32;
-  const void* fn = ex ? (const void*)attn_fwd_ml_kernel<HD, SP, true, DROP> : (const void*)attn_fwd_ml_kernel<HD, SP, false, DROP>;
-  if (sm > 64 * 1024 && !attr_set[ex]) {
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    attr_set[ex] = true;
-  }
+  constexpr size_t sm = fwd_smem<HD, SP>();
   const int BH = B * H;
   const int grid = (BH + FWD_ML_PAIRS - 1) / FWD_ML_PAIRS;
-  if (ex)
-    attn_fwd_ml_kernel<HD, SP, true, DROP><<<grid, 256, sm, st>>>(qkv, out, lse_out, S, H, BH, FWD_ML_PAIRS, scale, dr);
-  else
-    attn_fwd_ml_kernel<HD, SP, false, DROP><<<grid, 256, sm, st>>>(qkv, out, lse_out, S, H, BH, FWD_ML_PAIRS, scale, dr);
-  return 0;
+  return with_ex<SP>(S, [&](auto ex) {
+    constexpr bool EX = decltype(ex)::value;
+    lds_limit<attn_fwd_ml_kernel<HD, SP, EX, DROP>>(sm);
+    attn_fwd_ml_kernel<HD, SP, EX, DROP><<<grid, 256, sm, st>>>(qkv, out, lse_out, S, H, BH, FWD_ML_PAIRS, scale, dr);
+    return 0;
+  });
+}
+
+template <int HD, int SP, bool DROP>
+int run_drop(bool fwd, const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse_in, uint16_t* out,
+             float* lse_out, int B, int S, int H, float scale, AttnDrop dr, hipStream_t st) {
+  if (!fwd) return run_bwd<HD, SP, DROP>(qkv, o, dO, lse_in, out, lse_out, B, S, H, scale, dr, st);
+  if constexpr (SP <= 64) {
+    return run_fwd_ml<HD, SP, DROP>(qkv, out, lse_out, B, S, H, scale, dr, st);
+  } else {
+    return run_fwd<HD, SP, DROP>(qkv, out, lse_out, B, S, H, scale, dr, st);
+  }
 }
 
 template <int HD, int SP>
 int run(bool fwd, const uint16_t* qkv, const uint16_t* o, const uint16_t* dO, const float* lse_in, uint16_t* out,
         float* lse_out, int B, int S, int H, float scale, AttnDrop dr, hipStream_t st) {
-  if (dr.seed != nullptr) {
-    if (!fwd) return run_bwd<HD, SP, true>(qkv, o, dO, lse_in, out, lse_out, B, S, H, scale, dr, st);
-    if constexpr (SP <= 64) return run_fwd_ml<HD, SP, true>(qkv, out, lse_out, B, S, H, scale, dr, st);
-    return run_fwd<HD, SP, true>(qkv, out, lse_out, B, S, H, scale, dr, st);
-  }
-  if (!fwd) return run_bwd<HD, SP, false>(qkv, o, dO, lse_in, out, lse_out, B, S, H, scale, dr, st);
-  if constexpr (SP <= 64) return run_fwd_ml<HD, SP, false>(qkv, out, lse_out, B, S, H, scale, dr, st);
-  return run_fwd<HD, SP, false>(qkv, out, lse_out, B, S, H, scale, dr, st);
+  if (dr.seed != nullptr) return run_drop<HD, SP, true>(fwd, qkv, o, dO, lse_in, out, lse_out, B, S, H, scale, dr, st);
+  return run_drop<HD, SP, false>(fwd, qkv, o, dO, lse_in, out, lse_out, B, S, H, scale, dr, st);
 }
 
 template <int HD>
