@@ -6,6 +6,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <climits>
 
 #include "jm_api.h"
@@ -759,58 +760,62 @@ std::vector<torch::Tensor> recon(torch::Tensor pred, torch::Tensor images, torch
 }  // namespace
 
 // ------------------------------------------------------------------------------ GEMM
-// C[M, N] = A[M, K] . B[N, K]^T (+ bias) in bf16 (fp32 accumulate); gelu=true also returns
-// gelu(C) (the pre-activation C is what the backward needs).  A / B rows may be strided.
-// tail split (gemm.hip jm_gemm_nt_tail_plan): workspace for the split-K partials of the last,
-// partly filled wave of output tiles; returns the number of tail tiles (0 = plain launch)
-int attach_tail(GemmEpi& ep, torch::Tensor& ws, int M, int N, int K, int epi, const torch::Tensor& like) {
-  int r = 0;
-  long n = 0;
-  const int S = jm_gemm_nt_tail_plan(M, N, K, epi, like.stride(0), &r, &n);
-  if (S < 2) return 0;
-  ws = torch::empty({n}, like.options().dtype(torch::kFloat32));
-  ep.tail = ws.data_ptr<float>();
-  ep.tail_S = S;
-  ep.t_count = r;
-  return r;
+// Every NT launch: one plan (gemm_plan.h GemmPlan, jm_gemm_nt_plan) that sizes the buffers here and
+// that jm_gemm_nt obeys.
+// the bf16 operands A [M, K] and B [N, K], K contiguous (rows may be strided) -> {M, N, K}
+std::array<int, 3> check_nt_operands(const char* fn, const torch::Tensor& A, const torch::Tensor& B) {
+  CHECK_DT(A, torch::kBFloat16);
+  CHECK_DT(B, torch::kBFloat16);
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), fn, ": A [M,K], B [N,K]");
+  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1, fn, ": K must be contiguous");
+  return {(int)A.size(0), (int)B.size(0), (int)A.size(1)};
 }
 
+// the data of an optional contiguous fp32 [N] bias (or bias gradient); null without one
+float* bias_ptr(const char* what, const c10::optional<torch::Tensor>& bias, int N) {
+  if (!bias) return nullptr;
+  TORCH_CHECK(bias->is_contiguous() && bias->scalar_type() == torch::kFloat32 && bias->numel() == N, what);
+  return bias->data_ptr<float>();
+}
+
+// the planned launch, with the workspace of its tail split (GemmPlan::tail_floats)
+void run_nt(const char* fn, const GemmPlan& plan, const torch::Tensor& A, const torch::Tensor& B, GemmEpi ep) {
+  torch::Tensor ws;
+  if (plan.tail_floats) {
+    ws = torch::empty({plan.tail_floats}, A.options().dtype(torch::kFloat32));
+    ep.tail = ws.data_ptr<float>();
+  }
+  check_rc(jm_gemm_nt(plan, bf(A), bf(B), B.stride(0), ep, stream()), fn);
+}
+
+// C[M, N] = A[M, K] . B[N, K]^T (+ bias) in bf16 (fp32 accumulate); gelu=true also returns
+// gelu(C) (the pre-activation C is what the backward needs).  A / B rows may be strided.
 // gelu_deriv (with gelu): returns {gelu'(h) as uint8 codes (common.h gd_code), gelu(h)} instead of
 // {h, gelu(h)} (EPI_GELU_D); with dropout the codes are those of the kept gelu'(h) unscaled (0 where
 // dropped) and gemm_nt_dgelu applies 1 / keep when it decodes them
 std::vector<torch::Tensor> gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Tensor> bias, bool gelu,
                                    bool gelu_only, bool gelu_deriv, c10::optional<torch::Tensor> seed, double rate) {
-  CHECK_DT(A, torch::kBFloat16);
-  CHECK_DT(B, torch::kBFloat16);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_nt: A [M,K], B [N,K]");
-  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1, "gemm_nt: K must be contiguous");
-  const int M = A.size(0), N = B.size(0), K = A.size(1);
+  const auto [M, N, K] = check_nt_operands("gemm_nt", A, B);
   TORCH_CHECK(!gelu_deriv || N % 8 == 0, "gemm_nt: gelu_deriv needs N % 8 == 0");
   auto out = torch::empty({M, N}, gelu_deriv ? A.options().dtype(torch::kUInt8) : A.options());
   torch::Tensor out2;
-  GemmEpi ep{nullptr, gelu_deriv ? nullptr : bfm(out), N, nullptr, nullptr, nullptr, nullptr, 1};
+  GemmEpi ep{bias_ptr("gemm_nt bias", bias, N), gelu_deriv ? nullptr : bfm(out), N};
   if (gelu_deriv) ep.dq = out.data_ptr<uint8_t>();
-  if (bias) {
-    TORCH_CHECK(bias->is_contiguous() && bias->scalar_type() == torch::kFloat32 && bias->numel() == N, "gemm_nt bias");
-    ep.bias = bias->data_ptr<float>();
-  }
   if (gelu && !gelu_only) {
     out2 = torch::empty({M, N}, A.options());
     ep.out2 = bfm(out2);
   }
   TORCH_CHECK(!gelu_deriv || (gelu && !gelu_only), "gemm_nt: gelu_deriv needs gelu and not gelu_only");
-  const int epi = gelu_only ? 4 : (gelu_deriv ? 6 : (gelu ? 1 : 0));
+  const int epi = gelu_only ? EPI_GELU_ONLY : (gelu_deriv ? EPI_GELU_D : (gelu ? EPI_GELU : EPI_STORE));
   if (seed.has_value() && seed->defined() && rate > 0.0) {  // FF hidden dropout in the GELU_D epilogue
-    TORCH_CHECK(epi == 6, "gemm_nt: dropout only with gelu_deriv");
+    TORCH_CHECK(epi == EPI_GELU_D, "gemm_nt: dropout only with gelu_deriv");
     check_seed(*seed, A);
     const auto kp = keep_params(rate);
     ep.dseed = seed->data_ptr<int64_t>();
     ep.dthr = kp.first;
     ep.dscale = kp.second;
   }
-  torch::Tensor ws;
-  attach_tail(ep, ws, M, N, K, epi, A);
-  check_rc(jm_gemm_nt(bf(A), A.stride(0), bf(B), B.stride(0), M, N, K, epi, ep, stream()), "gemm_nt");
+  run_nt("gemm_nt", jm_gemm_nt_plan(M, N, K, epi, A.stride(0), 1), A, B, ep);
   if (gelu && !gelu_only) return {out, out2};
   return {out};
 }
@@ -820,20 +825,13 @@ std::vector<torch::Tensor> gemm_nt(torch::Tensor A, torch::Tensor B, c10::option
 // A.B^T (+ bias) + add, summed in the split-K reduction
 torch::Tensor gemm_nt_splitk(torch::Tensor A, torch::Tensor B, c10::optional<torch::Tensor> bias, int64_t splits,
                              c10::optional<torch::Tensor> add) {
-  CHECK_DT(A, torch::kBFloat16);
-  CHECK_DT(B, torch::kBFloat16);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_nt_splitk: A [M,K], B [N,K]");
-  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1, "gemm_nt_splitk: K must be contiguous");
-  const int M = A.size(0), N = B.size(0), K = A.size(1);
+  const auto [M, N, K] = check_nt_operands("gemm_nt_splitk", A, B);
   auto out = torch::empty({M, N}, A.options());
   auto part = torch::empty({splits, (long)M * N}, A.options().dtype(torch::kFloat32));
-  GemmEpi ep{nullptr, bfm(out), N, nullptr, nullptr, nullptr, part.data_ptr<float>(), (int)splits};
-  check_rc(jm_gemm_nt(bf(A), A.stride(0), bf(B), B.stride(0), M, N, K, 3, ep, stream()), "gemm_nt_splitk");
-  const float* bp = nullptr;
-  if (bias) {
-    TORCH_CHECK(bias->is_contiguous() && bias->scalar_type() == torch::kFloat32 && bias->numel() == N, "bias");
-    bp = bias->data_ptr<float>();
-  }
+  GemmEpi ep{nullptr, bfm(out), N};
+  ep.part = part.data_ptr<float>();
+  run_nt("gemm_nt_splitk", jm_gemm_nt_plan(M, N, K, EPI_PARTIAL, A.stride(0), (int)splits), A, B, ep);
+  const float* bp = bias_ptr("bias", bias, N);
   if (add) {
     CHECK_CUDA(*add);
     CHECK_DT(*add, torch::kFloat32);
@@ -853,14 +851,11 @@ torch::Tensor gemm_nt_splitk(torch::Tensor A, torch::Tensor B, c10::optional<tor
 // C[M, N] = A[M, K] . B[N, K]^T in fp32 (EPI_PARTIAL with one split: the accumulators stored as
 // they are) -- short-reduction weight gradients in NT form (ops/prims.py wgrad)
 torch::Tensor gemm_nt_f32(torch::Tensor A, torch::Tensor B) {
-  CHECK_DT(A, torch::kBFloat16);
-  CHECK_DT(B, torch::kBFloat16);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_nt_f32: A [M,K], B [N,K]");
-  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1, "gemm_nt_f32: K must be contiguous");
-  const int M = A.size(0), N = B.size(0), K = A.size(1);
+  const auto [M, N, K] = check_nt_operands("gemm_nt_f32", A, B);
   auto out = torch::empty({M, N}, A.options().dtype(torch::kFloat32));
-  GemmEpi ep{nullptr, nullptr, N, nullptr, nullptr, nullptr, out.data_ptr<float>(), 1};
-  check_rc(jm_gemm_nt(bf(A), A.stride(0), bf(B), B.stride(0), M, N, K, 3, ep, stream()), "gemm_nt_f32");
+  GemmEpi ep{nullptr, nullptr, N};
+  ep.part = out.data_ptr<float>();
+  run_nt("gemm_nt_f32", jm_gemm_nt_plan(M, N, K, EPI_PARTIAL, A.stride(0), 1), A, B, ep);
   return out;
 }
 
@@ -871,38 +866,42 @@ torch::Tensor gemm_nt_f32(torch::Tensor A, torch::Tensor B) {
 // kept derivative), 1 / keep applied with the decode
 torch::Tensor gemm_nt_dgelu(torch::Tensor A, torch::Tensor B, torch::Tensor pre, c10::optional<torch::Tensor> dbias,
                             bool deriv, double rate) {
-  CHECK_DT(A, torch::kBFloat16);
-  CHECK_DT(B, torch::kBFloat16);
   CHECK_DT(pre, deriv ? torch::kUInt8 : torch::kBFloat16);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "gemm_nt_dgelu: A [M,K], B [N,K]");
-  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1, "gemm_nt_dgelu: K must be contiguous");
-  const int M = A.size(0), N = B.size(0), K = A.size(1);
+  const auto [M, N, K] = check_nt_operands("gemm_nt_dgelu", A, B);
   TORCH_CHECK(pre.is_contiguous() && pre.size(0) == M && pre.size(1) == N, "gemm_nt_dgelu: pre [M,N]");
   auto out = torch::empty({M, N}, A.options());
-  torch::Tensor part;
-  GemmEpi ep{nullptr, bfm(out), N, nullptr, deriv ? nullptr : bf(pre), nullptr, nullptr, 1};
+  GemmEpi ep{nullptr, bfm(out), N};
   if (deriv) {
     ep.dqa = pre.data_ptr<uint8_t>();
-    ep.dqs = (rate > 0.0 ? keep_params(rate).second : 1.f) / 195.f;  // common.h GD_Q
+    ep.dqs = (rate > 0.0 ? keep_params(rate).second : 1.f) / GD_Q;
+  } else {
+    ep.aux = bf(pre);
   }
-  torch::Tensor ws;
-  const int epi = deriv ? 7 : 2;
-  const int r = attach_tail(ep, ws, M, N, K, epi, A);
-  int nM = jm_gemm_nt_colpart_rows(M, N, K, epi, A.stride(0));
-  if (dbias) {
-    TORCH_CHECK(dbias->is_contiguous() && dbias->scalar_type() == torch::kFloat32 && dbias->numel() == N,
-                "gemm_nt_dgelu dbias");
-    // tail tiles: their entries of the nM per-row-tile rows stay zero; the finish kernel writes
-    // 8 extra rows per tail tile
-    part = r ? torch::zeros({nM + 8 * r, N}, A.options().dtype(torch::kFloat32))
-             : torch::empty({nM, N}, A.options().dtype(torch::kFloat32));
+  GemmPlan plan = jm_gemm_nt_plan(M, N, K, deriv ? EPI_DMUL : EPI_DGELU, A.stride(0), 1);
+  float* db = bias_ptr("gemm_nt_dgelu dbias", dbias, N);
+  torch::Tensor part;  // the launch's column sums (GemmPlan::colpart_rows), added to dbias below
+  if (db) {
+    const auto f32 = A.options().dtype(torch::kFloat32);
+    part = plan.colpart_zero ? torch::zeros({plan.colpart_rows, N}, f32) : torch::empty({plan.colpart_rows, N}, f32);
     ep.colpart = part.data_ptr<float>();
-    nM += 8 * r;
+  } else {
+    plan.colpart = false;  // no bias gradient asked for: the kernels skip the column sums
   }
-  check_rc(jm_gemm_nt(bf(A), A.stride(0), bf(B), B.stride(0), M, N, K, epi, ep, stream()), "gemm_nt_dgelu");
-  if (dbias) check_rc(jm_splitk_reduce_add(part.data_ptr<float>(), dbias->data_ptr<float>(), N, nM, stream()),
-                      "gemm_nt_dgelu dbias");
+  run_nt("gemm_nt_dgelu", plan, A, B, ep);
+  if (db) check_rc(jm_splitk_reduce_add(part.data_ptr<float>(), db, N, plan.colpart_rows, stream()),
+                   "gemm_nt_dgelu dbias");
   return out;
+}
+
+// the plan's fields by name (tests, tools)
+py::dict gemm_nt_plan_dict(int M, int N, int K, int epi, long lda, int splits) {
+  const GemmPlan p = jm_gemm_nt_plan(M, N, K, epi, lda, splits);
+  using namespace py::literals;
+  return py::dict("status"_a = p.status, "family"_a = p.family, "tile_rows"_a = p.tile_rows,
+                  "tile_cols"_a = p.tile_cols, "row_tiles"_a = p.row_tiles, "col_tiles"_a = p.col_tiles,
+                  "tiles"_a = p.tiles, "grid"_a = p.grid, "tail_S"_a = p.tail_S, "tail_r"_a = p.tail_r,
+                  "tail_floats"_a = p.tail_floats, "colpart"_a = p.colpart, "colpart_rows"_a = p.colpart_rows,
+                  "colpart_zero"_a = p.colpart_zero);
 }
 
 // ---------------------------------------------------------------- augment (csrc/augment.hip)
@@ -1753,15 +1752,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_test_force", &jm_gemm_test_force, py::arg("path"), py::arg("rows") = 0,
         "numerics tests only: NT GEMM kernel path 0 = by shape, 1 = 64-deep main loop everywhere, "
         "2 = 4-phase kernels at every M without tail split (rows = forced tile height)");
-  m.def("gemm_nt_tiles", &jm_gemm_nt_tiles, py::arg("M"), py::arg("N"), py::arg("K") = 1024, py::arg("epi") = 0,
-        py::arg("lda") = 0, "output tiles (workgroups before split-K) of an NT launch");
+  m.def("gemm_nt_plan", &gemm_nt_plan_dict, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi") = 0,
+        py::arg("lda") = 0, py::arg("splits") = 1,
+        "the launch plan of an NT GEMM (csrc/gemm_plan.h GemmPlan) as a dict; read-only");
+  m.def(
+      "gemm_nt_tiles", [](int M, int N, int K, int epi, long lda) { return jm_gemm_nt_plan(M, N, K, epi, lda, 1).tiles; },
+      py::arg("M"), py::arg("N"), py::arg("K") = 1024, py::arg("epi") = 0, py::arg("lda") = 0,
+      "output tiles (workgroups before split-K) of an NT launch");
   m.def(
       "gemm_nt_tail_plan",
       [](int M, int N, int K, int epi, long lda) {
-        int r = 0;
-        long n = 0;
-        const int S = jm_gemm_nt_tail_plan(M, N, K, epi, lda, &r, &n);
-        return std::make_pair(S, r);
+        const GemmPlan p = jm_gemm_nt_plan(M, N, K, epi, lda, 1);
+        return std::make_pair(p.tail_S, p.tail_r);
       },
       py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi") = 0, py::arg("lda") = 0,
       "(S, tail tiles) of the tail split of an NT launch (S = 0: none); read-only");

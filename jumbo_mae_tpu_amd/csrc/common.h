@@ -145,9 +145,8 @@ JM_DEVICE void gelu_n(const float* x, float* g, float* d) {
 // gelu'(h) of the tanh GELU lies in [-0.1701, 1.1290].  The FF1 forward saves it for the FF2 data
 // gradient as an 8-bit code q = round(GD_Q gelu') + GD_Z -- step 1 / 195 = 0.0051, |error| <= 0.0026
 // (bf16 rounds values near 1 by up to 0.002), 0 and 1 exact (codes 34 and 229), codes 1..254 used --
-// half the bytes of a bf16 copy on both sides of the round trip (ops/prims.py GD_Q / GD_Z mirror).
-constexpr float GD_Q = 195.f;
-constexpr int GD_Z = 34;
+// half the bytes of a bf16 copy on both sides of the round trip (GD_Q / GD_Z: jm_api.h, which the
+// bindings see as well; ops/prims.py mirrors them).
 // v_cvt_pk_u8_f32 rounds to nearest even and saturates to [0, 255] (probed on gfx950:
 // tools/probes/cvt_pk_u8_probe.hip) and writes its byte into a word: one instruction per code
 // instead of the clamp / truncating convert / shift / or sequence -- the FF1 forward epilogue is

@@ -59,23 +59,6 @@ struct Frags {
 
 }  // namespace
 
-
-// EPI_STORE: out = acc (+bias); EPI_GELU: out = acc (+bias), out2 = gelu(out);
-// EPI_DGELU: out = bf16(acc) * gelu'(aux) -- the data gradient through the FF GELU -- with the
-// following Dense's bias gradient (column sums of out) as per-tile partials.
-// EPI_PARTIAL: split-K -- each (tile, split) workgroup stores its fp32 partial tile; the sum (+bias,
-// bf16) is taken by jm_splitk_reduce_bf16.  For small-M, long-K GEMMs (the jumbo MLP: 512 rows,
-// K = 12288) whose 24 output tiles would otherwise occupy 24 of 256 CUs.
-// EPI_GELU_ONLY: out = gelu(bf16(acc + bias)) alone -- inference (no backward needs the
-// pre-activation), half the epilogue bytes of EPI_GELU.
-// EPI_TAIL: split-K partial tile of a tail-split launch, stored compact in ep.tail (see GemmEpi).
-// EPI_GELU_D: dq = gelu'(h) as 8-bit codes (common.h gd_code), out2 = gelu(h) for h = bf16(acc + bias):
-// the FF1 forward saves the GELU derivative for the backward instead of h (one shared exp here, no
-// transcendental in the backward epilogue), in 1 byte per element instead of 2.
-// EPI_DMUL: out = bf16(acc) * gelu'(h) decoded from dqa, + column partials as EPI_DGELU.
-enum { EPI_STORE = 0, EPI_GELU = 1, EPI_DGELU = 2, EPI_PARTIAL = 3, EPI_GELU_ONLY = 4, EPI_TAIL = 5, EPI_GELU_D = 6,
-       EPI_DMUL = 7 };
-
 namespace {
 
 // FF hidden dropout of the EPI_GELU_D outputs (GemmEpi::dseed): W consecutive elements from flat
@@ -1123,9 +1106,11 @@ __global__ __launch_bounds__(256) void tail_finish_kernel(GemmEpi ep, int M, int
 
 
 constexpr int GEMM_GROUP = 8;  // row tiles per column sweep (profiles/r2_gemm_group.txt: 8 best)
+static_assert(BM == GEMM_PLAN_BM && BN == GEMM_PLAN_BN && NBM == GEMM_PLAN_NBM && NBN == GEMM_PLAN_NBN,
+              "gemm_plan.h plans for other tiles than the kernels'");
 // Kernel-path override for the numerics tests only (jm_gemm_test_force); production launches
 // choose by shape.  1: every launch on the 64-deep main loop (it otherwise runs at K % 128 == 64);
-// 2: the 4-phase kernels at every M, no tail split, g_test_rows = forced tile height (0 = tile_rows).
+// 2: the 4-phase kernels at every M, no tail split, g_test_rows = forced tile height (0 = by cost).
 int g_test_path = 0, g_test_rows = 0;
 int g_num_cus = 0;
 
@@ -1140,235 +1125,85 @@ int num_cus() {
   return g_num_cus;
 }
 
-template <int EPI, bool NTS>
-void launch_nt64(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, const GemmEpi& ep,
-                 int nwg, hipStream_t st) {
+// main-loop kernel FN on grid workgroups; its dynamic-LDS limit is raised once per instantiation
+template <auto FN>
+void launch(size_t smem, int grid, const GemmPlan& p, const uint16_t* A, const uint16_t* B, long ldb, const GemmEpi& ep,
+            hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<EPI, NTS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)GEMM_SMEM);
+    (void)hipFuncSetAttribute((const void*)FN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr = true;
   }
-  gemm_nt64_kernel<EPI, NTS><<<nwg, 512, GEMM_SMEM, st>>>(A, lda, B, ldb, M, N, K, ep, GEMM_GROUP);
+  FN<<<grid, 512, smem, st>>>(A, p.lda, B, ldb, p.M, p.N, p.K, ep, GEMM_GROUP);
 }
 
-template <int EPI, int MTL>
-void launch_p4(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, const GemmEpi& ep,
-               int nwg, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_p4_kernel<EPI, MTL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)GEMM_SMEM);
-    attr = true;
-  }
-  gemm_p4_kernel<EPI, MTL><<<nwg, 512, GEMM_SMEM, st>>>(A, lda, B, ldb, M, N, K, ep, GEMM_GROUP);
-}
-
+// the plan's kernel family and tile height with epilogue EPI
 template <int EPI>
-void launch_narrow(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, const GemmEpi& ep,
-                   hipStream_t st) {
-  static bool attr = false;
-  constexpr size_t sm = (size_t)N_RING * N_STAGE * 2;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_narrow_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)sm);
-    attr = true;
+void launch_main(const GemmPlan& p, const uint16_t* A, const uint16_t* B, long ldb, const GemmEpi& ep, hipStream_t st) {
+  if (p.family == GEMM_NARROW)
+    return launch<gemm_narrow_kernel<EPI>>((size_t)N_RING * N_STAGE * 2, p.grid, p, A, B, ldb, ep, st);
+  if (p.family == GEMM_NT64) return launch<gemm_nt64_kernel<EPI, true>>(GEMM_SMEM, p.grid, p, A, B, ldb, ep, st);
+  if constexpr (EPI != EPI_PARTIAL) {
+    if (p.tile_rows == 224) return launch<gemm_p4_kernel<EPI, 3>>(GEMM_SMEM, p.grid, p, A, B, ldb, ep, st);
+    if (p.tile_rows == 192) return launch<gemm_p4_kernel<EPI, 2>>(GEMM_SMEM, p.grid, p, A, B, ldb, ep, st);
+    if (p.tile_rows == 160) return launch<gemm_p4_kernel<EPI, 1>>(GEMM_SMEM, p.grid, p, A, B, ldb, ep, st);
   }
-  const int nwg = ((M + NBM - 1) / NBM) * ((N + NBN - 1) / NBN) * (EPI == EPI_PARTIAL ? ep.splits : 1);
-  gemm_narrow_kernel<EPI><<<nwg, 512, sm, st>>>(A, lda, B, ldb, M, N, K, ep, GEMM_GROUP);
+  return launch<gemm_p4_kernel<EPI, 4>>(GEMM_SMEM, p.grid, p, A, B, ldb, ep, st);
 }
 
-constexpr int NARROW_MAX_M = 4096;  // M below this: 128 x 192 tiles are a candidate
-
-bool p4_ok(int K, int epi, int splits) {
-  return g_test_path != 1 && K % 128 == 0 && (epi != EPI_PARTIAL || K / 128 >= splits);
-}
-
-// Relative cost per tile row of the short-row 4-phase tiles vs 256 rows (the same B panel feeds
-// fewer MFMAs; measured per full wave, profiles/r3_gemm_tile_rows.txt)
-// (160 rows: 1.20 -- ViT-B / finetune N = 768 GEMMs 5-6 % faster than 192 rows, the decoder's N = 512
-// ones 2 % slower than 224: profiles/r5_gemm_tile160.txt)
-float rows_cost(int tr) { return tr == 256 ? 1.f : (tr == 224 ? 1.05f : (tr == 192 ? 1.10f : 1.20f)); }
-
-// Cost per output element of the 128 x 192 narrow tile relative to the 4-phase 256-row tile: its
-// smaller tile re-reads operands 1.5-1.7x as often per FLOP (MFMA busy 35 vs 43-57 %, r4_gemm_pmc)
-constexpr float NARROW_COST = 1.45f;
-
-// M < NARROW_MAX_M: the narrow tiles unless a 4-phase launch fills the chip's waves better --
-// waves x tile outputs x per-output cost.  The jumbo MLP at a 2048-row micro-batch: N = 12288
-// runs 1.9 waves of 224-row tiles (16-20 % faster than 4 waves of narrow tiles), N = 3072 one
-// full wave of narrow tiles (a 224-row launch would leave half the chip idle); at 512 rows every
-// jumbo GEMM stays narrow (profiles/r4z_jumbo_routing.txt).  Split-K (EPI_PARTIAL) keeps the
-// narrow tiles: the jumbo MLP's K = 12288 GEMMs run 4 splits of 128 x 192 tiles instead of 10 of
-// 256 x 256 -- the GEMM alone is ~4 us slower (r3e_summary_vitl_b512_fused_reductions.txt) but the
-// fp32 partials shrink 2.5x (profiles/r3_narrow_splitk.txt: ViT-L step -0.41 ms in-process).
-bool narrow(int M, int N, int K, int epi) {
-  if (g_test_path != 0 || M >= NARROW_MAX_M || N % 8) return false;
-  if (epi == EPI_PARTIAL || epi == EPI_TAIL || !p4_ok(K, epi, 1)) return true;
-  const int ncu = num_cus();
-  const long tn = (long)((M + NBM - 1) / NBM) * ((N + NBN - 1) / NBN);
-  const float c_narrow = (float)((tn + ncu - 1) / ncu) * NBM * NBN * NARROW_COST;
-  const int nN = (N + BN - 1) / BN;
-  for (int tr : {256, 224, 192}) {
-    const long t = (long)((M + tr - 1) / tr) * nN;
-    if ((float)((t + ncu - 1) / ncu) * tr * BN * rows_cost(tr) < c_narrow) return false;
+// calls f with the epilogue as a compile-time constant (-3: not one that a caller may ask for)
+template <class F>
+int with_epi(int epi, F&& f) {
+  switch (epi) {
+    case EPI_STORE: return f(std::integral_constant<int, EPI_STORE>{});
+    case EPI_GELU: return f(std::integral_constant<int, EPI_GELU>{});
+    case EPI_DGELU: return f(std::integral_constant<int, EPI_DGELU>{});
+    case EPI_PARTIAL: return f(std::integral_constant<int, EPI_PARTIAL>{});
+    case EPI_GELU_ONLY: return f(std::integral_constant<int, EPI_GELU_ONLY>{});
+    case EPI_GELU_D: return f(std::integral_constant<int, EPI_GELU_D>{});
+    case EPI_DMUL: return f(std::integral_constant<int, EPI_DMUL>{});
   }
-  return true;
-}
-
-int tail_plan_256(int M, int N, int K, int epi, int* tail_r);
-
-// Tile height of a 4-phase launch: the candidate whose launch spans the fewest tile rows per CU,
-// waves x rows x rows_cost (a last wave that fills part of the chip costs a full wave; 256-row
-// launches may split a tail of at most a quarter wave instead, counted as 0.8 wave: the split
-// tail and its finish kernel lost to 224 / 192-row tiles on every measured shape).  Split-K,
-// tail-split and 64-deep launches and operands of >= 2 GB (the short tiles' unused a1 rows load
-// from offset 2^31, which must be out of range) keep 256.
-int tile_rows(int M, int N, int K, int epi, long lda) {
-  if (narrow(M, N, K, epi) || !p4_ok(K, epi, 1) || epi == EPI_PARTIAL || epi == EPI_TAIL) return BM;
-  if ((long)M * lda * 2 >= (1L << 31) - (1L << 20)) return BM;
-  if (g_test_rows) return g_test_rows;
-  const int ncu = num_cus(), nN = (N + BN - 1) / BN;
-  int r = 0;
-  const int t256 = ((M + BM - 1) / BM) * nN;
-  float best_c = tail_plan_256(M, N, K, epi, &r) ? (t256 / ncu + 0.8f) * BM : (float)((t256 + ncu - 1) / ncu) * BM;
-  int best = BM;
-  for (int tr : {224, 192, 160}) {
-    const int t = ((M + tr - 1) / tr) * nN;
-    const float c = (float)((t + ncu - 1) / ncu) * tr * rows_cost(tr);
-    if (c < best_c) best_c = c, best = tr;
-  }
-  return best;
-}
-
-// narrow tiles for M < 4096; K in 128-deep units (split-K: per split) -> p4 (256 / 224 / 192-row
-// tiles, tile_rows), else the 64-deep kernel (nontemporal epilogue stores)
-template <int EPI>
-void launch_epi(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, const GemmEpi& ep,
-                int nwg, hipStream_t st) {
-  if constexpr (EPI != EPI_TAIL) {
-    if (narrow(M, N, K, EPI) && ep.t_count == 0) return launch_narrow<EPI>(A, lda, B, ldb, M, N, K, ep, st);
-  }
-  if (p4_ok(K, EPI, ep.splits)) {
-    const int tr = ep.t_count > 0 ? BM : tile_rows(M, N, K, EPI, lda);
-    if constexpr (EPI != EPI_PARTIAL && EPI != EPI_TAIL) {
-      const int nw = ((M + tr - 1) / tr) * ((N + BN - 1) / BN);
-      if (tr == 224) return launch_p4<EPI, 3>(A, lda, B, ldb, M, N, K, ep, nw, st);
-      if (tr == 192) return launch_p4<EPI, 2>(A, lda, B, ldb, M, N, K, ep, nw, st);
-      if (tr == 160) return launch_p4<EPI, 1>(A, lda, B, ldb, M, N, K, ep, nw, st);
-    }
-    return launch_p4<EPI, 4>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  }
-  return launch_nt64<EPI, true>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-}
-
-template <int EPI>
-void launch_tail(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, const GemmEpi& ep,
-                 int tiles, hipStream_t st) {
-  const int r = ep.t_count;  // tail tiles
-  GemmEpi em = ep;
-  em.t_begin = 0;
-  em.t_count = tiles - r;
-  launch_epi<EPI>(A, lda, B, ldb, M, N, K, em, tiles - r, st);
-  GemmEpi et = ep;
-  et.t_begin = tiles - r;
-  launch_nt64<EPI_TAIL, false>(A, lda, B, ldb, M, N, K, et, r * ep.tail_S, st);
-  tail_finish_kernel<EPI><<<r * 8, 256, 0, st>>>(et, M, N, GEMM_GROUP);
+  return -3;
 }
 
 }  // namespace
 
 // numerics tests: path 0 = by shape, 1 = 64-deep main loop everywhere, 2 = 4-phase kernels at
-// every M without tail split (rows 256 / 224 / 192 forced, 0 = tile_rows)
+// every M without tail split (rows 256 / 224 / 192 / 160 forced, 0 = by cost)
 void jm_gemm_test_force(int path, int rows) {
   g_test_path = (path == 1 || path == 2) ? path : 0;
   g_test_rows = (g_test_path == 2 && (rows == 224 || rows == 192 || rows == 160 || rows == 256)) ? rows : 0;
 }
 
-// output tiles of an NT launch (the narrow kernel's 128 x 192 or the 4-phase 256 / 224 / 192 x 256)
-int jm_gemm_nt_tiles(int M, int N, int K, int epi, long lda) {
-  if (narrow(M, N, K, epi)) return ((M + NBM - 1) / NBM) * ((N + NBN - 1) / NBN);
-  const int tr = tile_rows(M, N, K, epi, lda);
-  return ((M + tr - 1) / tr) * ((N + BN - 1) / BN);
+GemmPlan jm_gemm_nt_plan(int M, int N, int K, int epi, long lda, int splits) {
+  return gemm_nt_plan(M, N, K, epi, lda, splits, num_cus(), g_test_path, g_test_rows);
 }
 
-// rows of the EPI_DGELU / EPI_DMUL column-partial buffer (one per row tile, before tail rows)
-int jm_gemm_nt_colpart_rows(int M, int N, int K, int epi, long lda) {
-  if (narrow(M, N, K, epi)) return (M + NBM - 1) / NBM;
-  const int tr = tile_rows(M, N, K, epi, lda);
-  return (M + tr - 1) / tr;
-}
-
-// Tail split plan for an NT launch: the last wave of output tiles (tiles % CUs of them) fills only
-// part of the chip; when it is at most a quarter wave, those tiles run split-K S ways (compact fp32
-// partials, *ws_floats) and a finish kernel applies the epilogue.  Returns S (0 = no tail split);
-// *tail_r = number of tail tiles.
-// ViT-B FF2 fwd 127 -> 109 us (profiles/r2_gemm_tail_p4.txt).
-namespace {
-int tail_plan_256(int M, int N, int K, int epi, int* tail_r) {
-  *tail_r = 0;
-  if (g_test_path != 0) return 0;
-  if (!(epi == EPI_STORE || epi == EPI_GELU || epi == EPI_DGELU || epi == EPI_GELU_ONLY) || N % 8 || K % 128) return 0;
-  if (narrow(M, N, K, epi)) return 0;
-  const int ncu = num_cus();
-  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  if (tiles < ncu) return 0;
-  const int r = tiles % ncu;
-  // (half a wave of tail tiles split 2 ways lost: ViT-L Wo 201 -> 224 us, step +5 ms, gpurun r4tl)
-  if (r == 0 || r > ncu / 4) return 0;
-  int S = ncu / r;
-  // every split keeps >= 8 64-deep K steps (r1: splits of 1-2 steps lost to the partial round trip,
-  // profiles/r1_gemm_tail_split.txt)
-  if (S > K / 512) S = K / 512;
-  if (S > 8) S = 8;
-  if (S < 2) return 0;
-  *tail_r = r;
-  return S;
-}
-}  // namespace
-
-int jm_gemm_nt_tail_plan(int M, int N, int K, int epi, long lda, int* tail_r, long* ws_floats) {
-  *tail_r = 0;
-  *ws_floats = 0;
-  if (tile_rows(M, N, K, epi, lda) != BM) return 0;  // short-row tiles fill the last wave instead
-  const int S = tail_plan_256(M, N, K, epi, tail_r);
-  *ws_floats = (long)S * *tail_r * BM * BN;
-  return S;
-}
-
-// returns 0 on success, <0 on unsupported shape
-int jm_gemm_nt(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int epi,
-               const GemmEpi& ep, hipStream_t st) {
-  if (K % 64 || N % 4 || M <= 0 || N <= 0) return -1;
-  if ((long)M * lda * 2 >= (1L << 32) || (long)N * ldb * 2 >= (1L << 32)) return -2;
-  const int nwg = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * (epi == EPI_PARTIAL ? ep.splits : 1);
-  if (epi == EPI_PARTIAL && (ep.splits < 1 || (K / 64) < ep.splits)) return -4;
-  if (ep.tail != nullptr && ep.tail_S >= 2 && ep.t_count > 0) {  // tail split (jm_gemm_nt_tail_plan)
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    if (epi == EPI_STORE) launch_tail<EPI_STORE>(A, lda, B, ldb, M, N, K, ep, tiles, st);
-    else if (epi == EPI_GELU) launch_tail<EPI_GELU>(A, lda, B, ldb, M, N, K, ep, tiles, st);
-    else if (epi == EPI_DGELU) launch_tail<EPI_DGELU>(A, lda, B, ldb, M, N, K, ep, tiles, st);
-    else if (epi == EPI_GELU_ONLY) launch_tail<EPI_GELU_ONLY>(A, lda, B, ldb, M, N, K, ep, tiles, st);
-    else return -3;
+// returns 0 on success, < 0: the plan's status, -2 B rows of 4 GiB or more, -5 a buffer that the plan needs
+// (ep.tail, ep.colpart) is missing
+int jm_gemm_nt(const GemmPlan& p, const uint16_t* A, const uint16_t* B, long ldb, const GemmEpi& ep, hipStream_t st) {
+  if (p.status) return p.status;
+  if ((long)p.N * ldb * 2 >= (1L << 32)) return -2;
+  if ((p.tail_S && ep.tail == nullptr) || p.colpart != (ep.colpart != nullptr)) return -5;
+  return with_epi(p.epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    GemmEpi em = ep;  // tail split: the main launch covers tiles [0, grid)
+    em.splits = p.splits;
+    em.tail_S = p.tail_S;
+    em.t_begin = 0;
+    em.t_count = p.tail_S ? p.grid : 0;
+    launch_main<EPI>(p, A, B, ldb, em, st);
+    if constexpr (gemm_tail_epi(EPI)) {
+      if (p.tail_S) {  // the tail tiles' split-K partials, then the epilogue over their sums
+        GemmEpi et = em;
+        et.t_begin = p.grid;
+        et.t_count = p.tail_r;
+        launch<gemm_nt64_kernel<EPI_TAIL, false>>(GEMM_SMEM, p.tail_r * p.tail_S, p, A, B, ldb, et, st);
+        tail_finish_kernel<EPI><<<p.tail_r * GEMM_PLAN_TAIL_BANDS, 256, 0, st>>>(et, p.M, p.N, GEMM_GROUP);
+      }
+    }
     return 0;
-  }
-  if (epi == EPI_PARTIAL)
-    launch_epi<EPI_PARTIAL>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else if (epi == EPI_STORE)
-    launch_epi<EPI_STORE>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else if (epi == EPI_GELU)
-    launch_epi<EPI_GELU>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else if (epi == EPI_GELU_ONLY)
-    launch_epi<EPI_GELU_ONLY>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else if (epi == EPI_DGELU && N % 8 == 0)
-    launch_epi<EPI_DGELU>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else if (epi == EPI_GELU_D)
-    launch_epi<EPI_GELU_D>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else if (epi == EPI_DMUL && N % 8 == 0)
-    launch_epi<EPI_DMUL>(A, lda, B, ldb, M, N, K, ep, nwg, st);
-  else
-    return -3;
-  return 0;
+  });
 }
 
 JM_DEBUG_EXPORT(gemm)

@@ -9,6 +9,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gemm_plan.h"  // GemmPlan and the EPI_* epilogue names (HIP-free, so that it compiles alone)
+
 // Dense-output dropout applied by the residual kernels that consume the branch output y (ops/blocks.py
 // Drops): the element at y + o (y's own element offset o) is kept with common.h drop_keep(seed, ioff + o),
 // kept values scaled by 1 / keep.  seed null: no dropout.
@@ -59,6 +61,11 @@ struct TnSegs {
   int n;
 };
 
+// The 8-bit code of gelu'(h): q = round(GD_Q gelu') + GD_Z (common.h gd_code, where the choice is explained;
+// ops/prims.py GD_Q / GD_Z mirror)
+constexpr float GD_Q = 195.f;
+constexpr int GD_Z = 34;
+
 // Epilogue / output description of an NT GEMM launch (gemm.hip, bindings.cpp).
 struct GemmEpi {
   const float* bias;     // [N] fp32 or null
@@ -66,12 +73,13 @@ struct GemmEpi {
   long ldo;
   uint16_t* out2;        // EPI_GELU: gelu(out) bf16 [M, ldo]
   const uint16_t* aux;   // EPI_DGELU: pre-activation h bf16 [M, ldo]
-  float* colpart;        // EPI_DGELU: per-row-tile column sums of out, [ceil(M/256) (+ 8 * tail tiles)][N] fp32
+  float* colpart;        // EPI_DGELU: per-row-tile column sums of out, [GemmPlan::colpart_rows][N] fp32
   float* part;           // EPI_PARTIAL: [splits][M][N] fp32 split-K partial products
   int splits;            // K splits (1 = none)
-  // tail split (jm_gemm_nt_tail_plan): the last, partly filled wave of output tiles is computed
-  // split-K into the compact workspace tail[tail_S][tail_r][256][256] and finished by a reduce
-  // kernel that applies the epilogue; t_begin / t_count restrict a launch to a tile range.
+  // tail split (GemmPlan): the last, partly filled wave of output tiles is computed split-K into
+  // the compact workspace tail[tail_S][tail_r][256][256] and finished by a reduce kernel that
+  // applies the epilogue; t_begin / t_count restrict a launch to a tile range.  The caller gives
+  // tail (GemmPlan::tail_floats floats); jm_gemm_nt fills splits, tail_S, t_begin and t_count
   float* tail;
   int tail_S;
   int t_begin;
@@ -255,15 +263,11 @@ int jm_recon(const void* pred, int pred_bf16, const uint8_t* img, const float* m
 int jm_debug_line_recon();
 
 // ---- gemm.hip
-// C = A[M, K] . B[N, K]^T on the MFMA kernels with epilogue epi (GemmEpi)
-int jm_gemm_nt(const uint16_t* A, long lda, const uint16_t* B, long ldb, int M, int N, int K, int epi,
-               const GemmEpi& ep, hipStream_t st);
-// output tiles (workgroups before split-K) of that launch
-int jm_gemm_nt_tiles(int M, int N, int K, int epi, long lda);
-// rows of its colpart output (EPI_DGELU)
-int jm_gemm_nt_colpart_rows(int M, int N, int K, int epi, long lda);
-// tail split of that launch: returns tail_S, *tail_r tiles, *ws_floats of workspace (0: none)
-int jm_gemm_nt_tail_plan(int M, int N, int K, int epi, long lda, int* tail_r, long* ws_floats);
+// the plan of the launch C = A[M, K] . B[N, K]^T with epilogue epi (EPI_*) on this device, under
+// jm_gemm_test_force: kernel family, tiles, grid, tail split, sizes of the tail and colpart buffers
+GemmPlan jm_gemm_nt_plan(int M, int N, int K, int epi, long lda, int splits);
+// that launch on the MFMA kernels, exactly as planned; ep: operands of the epilogue (GemmEpi)
+int jm_gemm_nt(const GemmPlan& plan, const uint16_t* A, const uint16_t* B, long ldb, const GemmEpi& ep, hipStream_t st);
 // numerics tests only: force a kernel path (0 = by shape)
 void jm_gemm_test_force(int path, int rows);
 int jm_debug_line_gemm();

@@ -162,20 +162,20 @@ _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc
 _ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused kernel (csrc/attn_stats.hip), else the torch composition
 
 
-NARROW_MAX_M = 4096  # csrc/gemm.hip NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles
+NARROW_MAX_M = 4096  # csrc/gemm_plan.h GEMM_NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles
 _NARROW_FUSED_MIN_TILES = 160  # a fused GELU epilogue needs the tiles alone to fill most CUs
 
 
 def nt_tiles(M: int, N: int) -> int:
     """Output tiles of an NT launch on the tiles its M selects (the split-K / fused-epilogue
-    decision below; jm_gemm_nt_tiles is exact: below NARROW_MAX_M the launch may take 4-phase
+    decision below; ext.gemm_nt_plan is exact: below NARROW_MAX_M the launch may take 4-phase
     tiles where they fill the chip's waves better, e.g. the N = 12288 jumbo GEMMs at M = 2048)."""
     if M < NARROW_MAX_M:
         return -(-M // 128) * -(-N // 192)
     return -(-M // 256) * -(-N // 256)
 
 
-def use_our_gemm(M: int, N: int, K: int, fused_gelu: bool = False, kind: str = "fwd") -> bool:
+def use_our_gemm(M: int, N: int, K: int, fused_gelu: bool = False) -> bool:
     """Every forward / data-gradient Dense runs on a hand-written MFMA GEMM (csrc/gemm.hip): M >=
     4096 on the 256 x 256 4-phase kernel (it matches or beats hipBLASLt on the ViT-L step as a
     whole, profiles/r2_gemm_routing.txt), smaller M on the 128 x 192 narrow kernel (the 512-row
@@ -446,10 +446,10 @@ def linear_dgrad(dy: torch.Tensor, hw: Handle, add: torch.Tensor | None = None) 
     if add is not None:
         return add + linear_dgrad(dy, hw).float()
     if (_DGRAD_OURS and hip(dy) and dy.dtype == torch.bfloat16
-            and use_our_gemm(dy.shape[0], w.shape[1], w.shape[0], kind="dgrad")):
+            and use_our_gemm(dy.shape[0], w.shape[1], w.shape[0])):
         return _ext.load().gemm_nt(dy.contiguous(), hw.weight_t(), None, False)[0]
     if (_DGRAD_OURS and hip(dy) and dy.dtype == torch.bfloat16 and w.shape[0] % 64
-            and use_our_gemm(dy.shape[0], w.shape[1], -(-w.shape[0] // 64) * 64, kind="dgrad")):
+            and use_our_gemm(dy.shape[0], w.shape[1], -(-w.shape[0] // 64) * 64)):
         # reduction dim (the Dense's output width, e.g. 1000 classes) zero-padded to 64-deep steps
         return _ext.load().gemm_nt(_pad_cols(dy), _pad_cols(hw.weight_t()), None, False)[0]
     return dy @ w
@@ -503,7 +503,7 @@ def linear_gelu_bwd(dy: torch.Tensor, g: torch.Tensor, pre: torch.Tensor, hw2: H
     M, N, K = dy.shape[0], w2.shape[1], w2.shape[0]
     if (_DGRAD_OURS and hip(dy) and dy.dtype == torch.bfloat16 and N % 8 == 0
             and (not deriv or pre.dtype == torch.uint8)  # a bf16 gelu' (unfused forward) takes gelu_bwd
-            and use_our_gemm(M, N, K, fused_gelu=True, kind="dgrad")):
+            and use_our_gemm(M, N, K, fused_gelu=True)):
         bg = hb1.grad if _trainable(hb1) else None
         dpre = _ext.load().gemm_nt_dgelu(dy.contiguous(), hw2.weight_t(), pre.contiguous(), bg, deriv, rate)
         linear_bwd(dy, g, hw2, hb2, need_dx=False, bias_done=bias2_done)
