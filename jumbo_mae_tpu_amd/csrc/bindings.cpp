@@ -1674,6 +1674,45 @@ torch::Tensor attn_stats(torch::Tensor qkv, int64_t heads, int64_t n_cls, c10::o
   return out;
 }
 
+// attention maps: one rollout step, r_out = alpha r_in + (1 - alpha) / H sum_h r_in softmax(q k^T / sqrt(hd))
+// (r_in fp32 [B, C, S], C <= 8); the [S, S] probabilities are never stored
+torch::Tensor attn_rollout_step(torch::Tensor qkv, int64_t heads, torch::Tensor r_in, double alpha,
+                                c10::optional<torch::Tensor> out_opt) {
+  TORCH_CHECK(qkv.is_cuda(), "attn_rollout_step: qkv must be a GPU tensor");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 && qkv.is_contiguous(),
+              "attn_rollout_step: qkv must be contiguous bf16");
+  check_attn_shape(qkv, heads, "attn_rollout_step");
+  const int64_t B = qkv.size(0), S = qkv.size(1), hd = qkv.size(2) / 3 / heads;
+  TORCH_CHECK(B >= 1 && S >= 1 && B < INT_MAX && S < INT_MAX && heads < INT_MAX,
+              "attn_rollout_step: empty or oversized qkv");
+  TORCH_CHECK(r_in.is_cuda() && r_in.device() == qkv.device() && r_in.scalar_type() == torch::kFloat32 &&
+                  r_in.is_contiguous() && r_in.dim() == 3 && r_in.size(0) == B && r_in.size(2) == S,
+              "attn_rollout_step: r_in must be a contiguous fp32 [B, C, S] tensor on qkv's GPU");
+  const int64_t C = r_in.size(1);
+  TORCH_CHECK(C >= 1 && C <= 8, "attn_rollout_step: C must be in 1..8 (got ", C, ")");
+  TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "attn_rollout_step: alpha must be in [0, 1] (got ", alpha, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "attn_rollout_step: qkv must be 16-byte aligned");
+  const long nw = jm_attn_rollout_ws((int)B, (int)S, (int)heads, (int)C);
+#ifdef JM_DEBUG
+  auto ws = torch::zeros({nw}, r_in.options());  // a workgroup stopped by its guard adds nothing
+#else
+  auto ws = torch::empty({nw}, r_in.options());
+#endif
+  torch::Tensor out;
+  if (out_opt.has_value() && out_opt->defined()) {
+    out = *out_opt;
+    TORCH_CHECK(out.is_cuda() && out.device() == qkv.device() && out.scalar_type() == torch::kFloat32 &&
+                    out.is_contiguous() && out.sizes() == r_in.sizes() && out.data_ptr() != r_in.data_ptr(),
+                "attn_rollout_step: out must be a contiguous fp32 [B, C, S] tensor on qkv's GPU, distinct from r_in");
+  } else {
+    out = torch::empty_like(r_in);
+  }
+  check_rc(jm_attn_rollout_step(qkv.data_ptr(), (int)B, (int)S, (int)heads, (int)hd, r_in.data_ptr<float>(), (int)C,
+                                alpha, out.data_ptr<float>(), ws.data_ptr<float>(), stream()),
+           "attn_rollout_step");
+  return out;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1685,7 +1724,7 @@ py::dict debug_lines() {
       {"layernorm", jm_debug_line_layernorm}, {"loss", jm_debug_line_loss},
       {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
       {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
-      {"attn_stats", jm_debug_line_attn_stats}};
+      {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1825,6 +1864,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_block_cols", &jm_bn_block_cols, "columns per workgroup of the BatchNorm kernels");
   m.def("attn_stats", &attn_stats, py::arg("qkv"), py::arg("heads"), py::arg("n_cls"),
         py::arg("rows_out") = py::none(), "per-head attention statistics, fp64 [H, 6]");
+  m.def("attn_rollout_step", &attn_rollout_step, py::arg("qkv"), py::arg("heads"), py::arg("r_in"), py::arg("alpha"),
+        py::arg("out") = py::none(), "one attention-rollout step on fp32 rows [B, C, S] (C <= 8) -> fp32 [B, C, S]");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

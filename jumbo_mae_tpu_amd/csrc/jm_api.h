@@ -402,3 +402,13 @@ int jm_attn_stats(const void* qkv, int B, int S, int H, int hd, int n_cls, doubl
 // out (fp64 [H, 6]) = the partials added per head in (b, tile) order with a fixed tree
 int jm_attn_stats_finish(const double* part, int B, int S, int H, double* out, hipStream_t st);
 int jm_debug_line_attn_stats();
+
+// ---- attn_rollout.hip (qkv as for attn_stats.hip; r_in, r_out: fp32 [B, C, S] contiguous and distinct, 1 <= C <= 8;
+// 0 <= alpha <= 1; -1 bad argument or a batch element of 2 GiB or more, -2 failed launch)
+// floats of the workspace ws (16-byte aligned): (max, 1 / sum e) per attention row [B, H, S, 2], then the per-head
+// partials [B, H, C, S]
+long jm_attn_rollout_ws(int B, int S, int H, int C);
+// r_out[b, c, k] = alpha r_in[b, c, k] + (1 - alpha) / H sum_h sum_q r_in[b, c, q] softmax_k(q k^T / sqrt(hd))[b, h, q, k]
+int jm_attn_rollout_step(const void* qkv, int B, int S, int H, int hd, const float* r_in, int C, double alpha,
+                         float* r_out, float* ws, hipStream_t st);
+int jm_debug_line_attn_rollout();

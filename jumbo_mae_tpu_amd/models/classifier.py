@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from ..config import ViTConfig
+from ..ops import attn_maps as AM
 from ..ops import attn_stats as AS
 from ..ops import functional as Fn
 from ..ops import mae as mae_ops
@@ -172,6 +173,16 @@ class FinetuneModel:
         names = [f"layer_{i}" for i in range(len(self.encoder.layers))]
         return AS.collect_layers(names, lambda: self.features(rows, images_u8.shape[0], None, True),
                                  self.cfg.num_cls_tokens)
+
+    @torch.no_grad()
+    def attention_maps(self, images_u8, alpha: float = 0.5, mode: str = "rollout") -> dict:
+        """``{"maps": fp32 [B, n_cls, gh, gw], "cls_mass": fp32 [B, n_cls]}`` (ops/attn_maps.py): the CLS
+        attention rollout (``mode="last"``: the last layer's head-mean CLS attention) from one ``det=True``
+        encoder forward of the unmixed images, as in ``attention_stats``; the head does not run."""
+        rows, _ = self.patches(images_u8, None, None, True, plan=None)
+        got = AM.collect_layers(lambda: self.features(rows, images_u8.shape[0], None, True), len(self.encoder.layers))
+        g = self.cfg.grid
+        return AM.maps_and_mass(got, got.heads, self.cfg.num_cls_tokens, g, g, alpha, mode)
 
     @torch.no_grad()
     def evaluate(self, images_u8, labels, rngs=None) -> dict:

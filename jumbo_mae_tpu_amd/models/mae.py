@@ -19,6 +19,7 @@ import torch
 
 from ..config import DecoderConfig, ViTConfig
 from ..data.constants import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
+from ..ops import attn_maps as AM
 from ..ops import attn_stats as AS
 from ..ops import mae as mae_ops
 from ..utils.mae import masking_ids
@@ -138,6 +139,16 @@ class PretrainModel:
                 [f"decoder/dec_layer_{i}" for i in range(len(self.decoder.layers))]
         return AS.collect_layers(names, lambda: self._predict(images_u8, {}, True, True, noise),
                                  self.cfg.num_cls_tokens)
+
+    @torch.no_grad()
+    def attention_maps(self, images_u8: torch.Tensor, alpha: float = 0.5, mode: str = "rollout") -> dict:
+        """``{"maps": fp32 [B, n_cls, gh, gw], "cls_mass": fp32 [B, n_cls]}`` (ops/attn_maps.py): the CLS
+        attention rollout (``mode="last"``: the last layer's head-mean CLS attention) over the encoder, from
+        the forward ``features`` runs: every patch (no masking), ``det=True``.  The decoder does not run and
+        no random stream is touched."""
+        got = AM.collect_layers(lambda: self.features(images_u8), len(self.encoder.layers))
+        g = self.cfg.grid
+        return AM.maps_and_mass(got, got.heads, self.cfg.num_cls_tokens, g, g, alpha, mode)
 
     @torch.no_grad()
     def evaluate(self, images_u8: torch.Tensor, valid: torch.Tensor | None = None, rngs: dict | None = None) -> dict:

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ..config import DecoderConfig, ViTConfig
+from ..ops import attn_maps as AM
 from ..ops import attn_stats as AS
 from ..ops import blocks
 from ..ops import dropout as Dr
@@ -110,6 +111,8 @@ class Attention:
         qkv = Fn.linear(x2d, self.qkv_k, self.qkv_b).view(B, S, 3 * self.dim)
         if AS._COLLECTOR is not None:  # the attention monitor's probe pass (ops/attn_stats.py collecting)
             AS.observe(qkv, self.heads)
+        if AM._COLLECTOR is not None:  # the attention maps' probe pass (ops/attn_maps.py collecting)
+            AM.observe(qkv, self.heads)
         if self.dropout > 0 and not det:
             o = _attention_with_dropout(qkv, self.heads, self.dropout, rng, seeds and seeds[0])
         else:

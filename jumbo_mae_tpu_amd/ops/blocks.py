@@ -23,6 +23,7 @@ import torch
 
 from typing import NamedTuple
 
+from . import attn_maps as AM
 from . import attn_stats as AS
 from . import dropout as Dr
 from . import prims as P
@@ -100,6 +101,8 @@ def _attn_fwd(attn, h1, B, S, dr: Drops | None = None):
     qkv = P.linear_fwd(h1, attn.qkv_k, attn.qkv_b)
     if AS._COLLECTOR is not None:  # the attention monitor's probe pass (ops/attn_stats.py collecting)
         AS.observe(qkv.view(B, S, -1), attn.heads)
+    if AM._COLLECTOR is not None:  # the attention maps' probe pass (ops/attn_maps.py collecting)
+        AM.observe(qkv.view(B, S, -1), attn.heads)
     o, lse = P.attn_fwd(qkv.view(B, S, -1), attn.heads, drop=(dr.attn, dr.rate) if dr is not None else None)
     a = P.linear_fwd(o.view(B * S, -1), attn.wo_k, attn.wo_b)
     return qkv, o, lse, a

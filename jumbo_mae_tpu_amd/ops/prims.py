@@ -160,6 +160,7 @@ _BN_OURS = True  # linear-probe BatchNorm on the fused kernels (csrc/batchnorm.h
 _KNN_OURS = True  # k-NN monitor's top-k and vote on the fused kernels (csrc/knn.hip), else the torch composition
 _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc/optim.hip seg_stats), else the torch composition
 _ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused kernel (csrc/attn_stats.hip), else the torch composition
+_ATTN_MAPS_OURS = True  # attention maps' rollout step on the fused kernels (csrc/attn_rollout.hip), else the torch composition
 
 
 NARROW_MAX_M = 4096  # csrc/gemm_plan.h GEMM_NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles

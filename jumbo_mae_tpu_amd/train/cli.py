@@ -134,6 +134,14 @@ def _extensions(p: argparse.ArgumentParser):
                         "heads; uniform attention = log S), attn/entropy_min/<layer> (the lowest head), "
                         "attn/max_logit/<layer>, attn/max_prob/<layer>, attn/cls_mass/<layer>, and over the layers "
                         "val/attn_entropy_min and val/attn_max_logit (ops/attn_stats.py); 0 = off")
+    g.add_argument("--attn-maps", type=int, default=0,
+                   help="at every evaluation rank 0 runs the first N validation images (unmasked) through the "
+                        "encoder once more, writes {output_dir}/{name}-attn-{step:07d}.png (one row per image: the "
+                        "original, then one heat-map overlay per CLS token) and logs val/attn_map_entropy (nats, of "
+                        "the patch map normalised to sum 1) and val/attn_map_cls_mass (ops/attn_maps.py); 0 = off")
+    g.add_argument("--attn-maps-mode", default="rollout", choices=["rollout", "last"],
+                   help="rollout: CLS attention rollout over the encoder's layers (residual weight 0.5); "
+                        "last: the head-mean attention of the CLS rows in the last layer")
     return g
 
 

@@ -331,3 +331,68 @@ def evaluate_attn_stats(model, loader, args, device, log) -> dict:
         log("[eval] " + line)
     return vals
 
+
+def attn_map_ramp():
+    """The fixed colour ramp of the attention overlays, uint8 [256, 3]: piecewise linear through black,
+    purple, red, orange, yellow, white."""
+    import numpy as np
+
+    stops = np.array([[0, 0, 0], [84, 15, 109], [187, 55, 84], [249, 142, 8], [252, 230, 60], [255, 255, 255]], float)
+    x = np.linspace(0.0, len(stops) - 1.0, 256)
+    i = np.minimum(x.astype(int), len(stops) - 2)
+    f = (x - i)[:, None]
+    return np.round(stops[i] * (1.0 - f) + stops[i + 1] * f).astype(np.uint8)
+
+
+def attn_map_panel(images_u8: torch.Tensor, maps: torch.Tensor, blend: float = 0.6):
+    """PIL image with one row per input image: original | one heat-map overlay per CLS token.  Each map
+    ``[gh, gw]`` is divided by its max, nearest-upsampled by the patch size, coloured by ``attn_map_ramp``
+    and blended over the image with weight ``blend`` (NumPy and PIL only)."""
+    import numpy as np
+    from PIL import Image
+
+    img = images_u8.permute(0, 2, 3, 1).cpu().numpy().astype(np.float64)  # [B, S, S, 3]
+    m = maps.detach().double().cpu().numpy()  # [B, C, gh, gw]
+    B, C, gh, gw = m.shape
+    ph, pw = img.shape[1] // gh, img.shape[2] // gw
+    top = m.reshape(B, C, -1).max(-1)[:, :, None, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        u = np.where(top > 0, m / top, 0.0)
+    idx = np.clip(np.nan_to_num(np.round(u * 255.0), nan=0.0), 0, 255).astype(np.int64)
+    heat = attn_map_ramp()[idx].astype(np.float64)  # [B, C, gh, gw, 3]
+    heat = heat.repeat(ph, 2).repeat(pw, 3)
+    cols = [img]
+    for c in range(C):
+        over = img.copy()
+        over[:, :gh * ph, :gw * pw] = (1.0 - blend) * img[:, :gh * ph, :gw * pw] + blend * heat[:, c]
+        cols.append(over)
+    rows = np.concatenate(cols, 2)  # [B, S, (1 + C) S, 3]
+    return Image.fromarray(np.ascontiguousarray(np.round(rows).astype(np.uint8).reshape(-1, rows.shape[2], 3)))
+
+
+def attn_map_values(out: dict) -> dict:
+    """``val/attn_map_entropy``: the mean over images and CLS tokens of the entropy (nats) of the patch map
+    normalised to sum 1; ``val/attn_map_cls_mass``: the mean mass left on the CLS tokens."""
+    m = out["maps"].double().flatten(2)
+    p = m / m.sum(-1, keepdim=True)
+    ent = -torch.where(p > 0, p * torch.log(p), torch.zeros_like(p)).sum(-1)
+    return {"val/attn_map_entropy": float(ent.mean()), "val/attn_map_cls_mass": float(out["cls_mass"].double().mean())}
+
+
+def evaluate_attn_maps(model, loader, args, device, step: int, log) -> dict:
+    """--attn-maps (rank 0 only, no collectives): the attention maps (``model.attention_maps``,
+    --attn-maps-mode) of the first N validation images, unmasked; writes
+    ``{output_dir}/{name}-attn-{step:07d}.png`` and returns ``val/attn_map_entropy`` and
+    ``val/attn_map_cls_mass``.  Nothing is taken from the training streams."""
+    import os
+
+    with torch.random.fork_rng(devices=[]):  # a loader iterator seeds its workers from the default generator
+        images = first_images(loader, args.attn_maps, device)
+    out = model.attention_maps(images, mode=args.attn_maps_mode)
+    if gopen.is_local(args.output_dir or "."):
+        os.makedirs(args.output_dir or ".", exist_ok=True)
+        path = os.path.join(args.output_dir or ".", f"{args.name or 'run'}-attn-{step:07d}.png")
+        attn_map_panel(images, out["maps"]).save(path)
+    else:
+        log(f"[eval] --attn-maps: remote --output-dir {args.output_dir}, attention-map PNG skipped")
+    return attn_map_values(out)

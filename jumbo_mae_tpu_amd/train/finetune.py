@@ -14,7 +14,9 @@ Parity: /root/reference/src/main_finetune.py:37-94 and create_train_state
   * ``--log-norms global|layer`` (extension): gradient / weight / update norms of every logged step
     (optim/monitor.py), written before the non-finite check so that an abort names its leaves;
   * ``--attn-stats N`` (extension): at every evaluation rank 0 logs the per-layer attention entropy,
-    largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py).
+    largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py);
+  * ``--attn-maps N`` (extension): at every evaluation rank 0 writes the CLS attention maps of the first N
+    validation images as a PNG panel and logs their entropy and CLS mass (ops/attn_maps.py).
 """
 
 from __future__ import annotations
@@ -129,6 +131,8 @@ def main(args) -> dict:
             result["val/ema_acc1/best"] = resumed.best("val/ema_acc1", 0.0)  # nothing is saved here
         if args.attn_stats > 0 and info.is_main:
             result.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
+        if args.attn_maps > 0 and info.is_main:
+            result.update(C.evaluate_attn_maps(model, valid_loader, args, device, start, log))
         logger.log(dict(result), start)
         log(f"[eval] step {start} {result}")
     meter = AverageMeter(use_latest=["learning_rate"])
@@ -182,6 +186,8 @@ def main(args) -> dict:
             if info.is_main:
                 if args.attn_stats > 0:
                     res.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
+                if args.attn_maps > 0:
+                    res.update(C.evaluate_attn_maps(model, valid_loader, args, device, step, log))
                 res["val/acc1/best"] = max_acc1
                 if ema is not None:
                     res["val/ema_acc1/best"] = max_ema_acc1

@@ -12,7 +12,9 @@ Parity: /root/reference/src/main_pretrain.py:37-94 and create_train_state
   * ``--log-norms global|layer`` (extension): gradient / weight / update norms of every logged step
     (optim/monitor.py), written before the non-finite check so that an abort names its leaves;
   * ``--attn-stats N`` (extension): at every evaluation rank 0 logs the per-layer attention entropy,
-    largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py).
+    largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py);
+  * ``--attn-maps N`` (extension): at every evaluation rank 0 writes the CLS attention maps of the first N
+    validation images (unmasked) as a PNG panel and logs their entropy and CLS mass (ops/attn_maps.py).
 Launch: ``torchrun --nproc-per-node 8 src/main_pretrain.py <reference flags>``.
 """
 
@@ -186,6 +188,8 @@ def main(args) -> dict:
             result.update(evaluate_recon(model, valid_loader, args, device, start, log))
         if args.attn_stats > 0 and info.is_main:
             result.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
+        if args.attn_maps > 0 and info.is_main:
+            result.update(C.evaluate_attn_maps(model, valid_loader, args, device, start, log))
         logger.log(dict(result), start)
         log(f"[eval] step {start} {result}")
     meter = AverageMeter(use_latest=["learning_rate"])
@@ -235,6 +239,8 @@ def main(args) -> dict:
                     res.update(evaluate_recon(model, valid_loader, args, device, step, log))
                 if args.attn_stats > 0:
                     res.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
+                if args.attn_maps > 0:
+                    res.update(C.evaluate_attn_maps(model, valid_loader, args, device, step, log))
                 res["val/loss/best"] = min_val_loss
                 res["processed_samples"] = step * args.train_batch_size
                 logger.log(res, step)
