@@ -1370,6 +1370,71 @@ torch::Tensor cls_loss_bwd(torch::Tensor dloss, torch::Tensor logits, torch::Ten
   return dlogits;
 }
 
+// ------------------------------------------------------------------------------ distillation loss
+// Shared argument checks of kd_loss_fwd / kd_loss_bwd (u may be undefined where the caller allows it)
+static void check_kd_logits(const torch::Tensor& t, const char* what) {
+  CHECK_CUDA(t);
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32, "kd_loss: ", what,
+              " must be bf16 or fp32");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1, "kd_loss: ", what, " must be [B, L]");
+  TORCH_CHECK(t.stride(1) == 1, "kd_loss: ", what, " must have a unit column stride");
+  TORCH_CHECK(t.size(0) == 1 || t.stride(0) >= t.size(1), "kd_loss: ", what, " rows must not overlap");
+  TORCH_CHECK(t.size(0) < INT_MAX && t.size(1) < INT_MAX, "kd_loss: ", what, " too large");
+}
+
+static void check_kd(const torch::Tensor& z, const torch::Tensor* u, double temp, int64_t mode) {
+  check_kd_logits(z, "z");
+  if (u) {
+    check_kd_logits(*u, "u");
+    TORCH_CHECK(u->device() == z.device() && u->scalar_type() == z.scalar_type() && u->sizes() == z.sizes(),
+                "kd_loss: u must have the dtype, shape and device of z");
+  }
+  TORCH_CHECK(mode == 0 || mode == 1, "kd_loss: mode 0 (soft) or 1 (hard)");
+  TORCH_CHECK(temp > 0.0 && std::isfinite(temp), "kd_loss: the temperature must be positive");
+}
+
+// [kd fp32 [B], agree bool [B], lse fp32 [B, 4], t int32 [B] (the teacher's arg-max)]
+std::vector<torch::Tensor> kd_loss_fwd(torch::Tensor z, torch::Tensor u, double temp, int64_t mode) {
+  check_kd(z, &u, temp, mode);
+  const int64_t B = z.size(0);
+  auto kd = torch::empty({B}, z.options().dtype(torch::kFloat32));
+  auto agree = torch::empty({B}, z.options().dtype(torch::kBool));
+  auto lse = torch::empty({B, 4}, z.options().dtype(torch::kFloat32));
+  auto targ = torch::empty({B}, z.options().dtype(torch::kInt32));
+  check_rc(jm_kd_loss_fwd(z.data_ptr(), row_stride(z), u.data_ptr(), row_stride(u),
+                          z.scalar_type() == torch::kBFloat16, temp, (int)mode, (int)B, (int)z.size(1),
+                          kd.data_ptr<float>(), reinterpret_cast<uint8_t*>(agree.data_ptr()), lse.data_ptr<float>(),
+                          targ.data_ptr<int>(), stream()),
+           "kd_loss_fwd");
+  return {kd, agree, lse, targ};
+}
+
+// dz [B, L] contiguous, in the dtype of z; u: soft mode only, t: hard mode only
+torch::Tensor kd_loss_bwd(torch::Tensor dloss, torch::Tensor z, c10::optional<torch::Tensor> u, double temp,
+                          int64_t mode, torch::Tensor lse, c10::optional<torch::Tensor> t) {
+  const bool hu = u.has_value() && u->defined(), ht = t.has_value() && t->defined();
+  check_kd(z, hu ? &*u : nullptr, temp, mode);
+  const int64_t B = z.size(0), L = z.size(1);
+  TORCH_CHECK(mode == 0 ? hu : ht, "kd_loss_bwd: soft mode needs u, hard mode needs t");
+  TORCH_CHECK(lse.device() == z.device() && lse.scalar_type() == torch::kFloat32 && lse.dim() == 2 &&
+                  lse.size(0) == B && lse.size(1) == 4 && lse.is_contiguous(),
+              "kd_loss_bwd: lse must be the forward's fp32 [B, 4]");
+  TORCH_CHECK(dloss.device() == z.device() && dloss.scalar_type() == torch::kFloat32 && dloss.dim() == 1 &&
+                  dloss.size(0) == B && dloss.is_contiguous(),
+              "kd_loss_bwd: dloss must be fp32 [B] on the logits' device");
+  if (mode == 1)
+    TORCH_CHECK(t->device() == z.device() && t->scalar_type() == torch::kInt32 && t->dim() == 1 && t->size(0) == B &&
+                    t->is_contiguous(),
+                "kd_loss_bwd: t must be the forward's int32 [B]");
+  auto dz = torch::empty({B, L}, z.options());
+  const bool soft = mode == 0;
+  check_rc(jm_kd_loss_bwd(z.data_ptr(), row_stride(z), soft ? u->data_ptr() : nullptr, soft ? row_stride(*u) : 0,
+                          z.scalar_type() == torch::kBFloat16, temp, (int)mode, (int)B, (int)L, lse.data_ptr<float>(),
+                          soft ? nullptr : t->data_ptr<int>(), dloss.data_ptr<float>(), dz.data_ptr(), L, stream()),
+           "kd_loss_bwd");
+  return dz;
+}
+
 // ------------------------------------------------------------------------------ batch norm
 // Argument checks of the bn_* entry points.  Dtypes, shapes and strides are checked before the
 // devices, and everything before any launch, so each message can be reached with CPU tensors.
@@ -1724,7 +1789,8 @@ py::dict debug_lines() {
       {"layernorm", jm_debug_line_layernorm}, {"loss", jm_debug_line_loss},
       {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
       {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
-      {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout}};
+      {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout},
+      {"distill", jm_debug_line_distill}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1843,6 +1909,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w") = py::none(), py::arg("smoothing") = 0.0, py::arg("mode") = 0);
   m.def("cls_loss_bwd", &cls_loss_bwd, py::arg("dloss"), py::arg("logits"), py::arg("labels"),
         py::arg("perm"), py::arg("w"), py::arg("smoothing"), py::arg("mode"), py::arg("lse"));
+  m.def("kd_loss_fwd", &kd_loss_fwd, py::arg("z"), py::arg("u"), py::arg("temperature") = 1.0, py::arg("mode") = 0,
+        "distillation loss -> (kd fp32 [B], agree bool [B], lse fp32 [B, 4], t int32 [B])");
+  m.def("kd_loss_bwd", &kd_loss_bwd, py::arg("dloss"), py::arg("z"), py::arg("u"), py::arg("temperature"),
+        py::arg("mode"), py::arg("lse"), py::arg("t") = py::none());
   m.def("knn_topk", &knn_topk, py::arg("q"), py::arg("bank"), py::arg("k"), py::arg("self_idx") = py::none(),
         py::arg("splits") = 0, py::arg("out_idx") = py::none(), py::arg("out_sim") = py::none(),
         "fused similarity + top-k -> (idx int32, sim fp32) [Nq, k], ties by ascending bank index");

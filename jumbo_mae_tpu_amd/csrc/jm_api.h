@@ -345,6 +345,19 @@ int jm_cls_loss_bwd(const void* logits, int bf16, long ld, const int64_t* labels
                     long ldo, hipStream_t st);
 int jm_debug_line_loss();
 
+// ---- distill.hip (z student / u teacher logits: both bf16 or both fp32, [B, L], rows ldz / ldu elements apart;
+// temp > 0; mode 0 = soft (temperature-scaled KL), 1 = hard (CE against the teacher's arg-max, temp unused);
+// -1 bad argument, -2 failed launch)
+// kd fp32 [B], agree bytes [B] (arg-max z == arg-max u, lowest index on ties), lse fp32 [B, 4] = (hi, lo) pairs of
+// lse(z / temp), lse(u / temp) (hard: lse(z), zeros), targ int32 [B] = arg-max u
+int jm_kd_loss_fwd(const void* z, long ldz, const void* u, long ldu, int bf16, double temp, int mode, int B, int L,
+                   float* kd, uint8_t* agree, float* lse, int* targ, hipStream_t st);
+// dz [B, L] (rows ldo apart, the dtype of z) = dloss[b] times the gradient of row b's kd; u is read in soft mode
+// only (may be null in hard mode), targ in hard mode only (may be null in soft mode)
+int jm_kd_loss_bwd(const void* z, long ldz, const void* u, long ldu, int bf16, double temp, int mode, int B, int L,
+                   const float* lse, const int* targ, const float* dloss, void* dz, long ldo, hipStream_t st);
+int jm_debug_line_distill();
+
 // ---- batchnorm.hip (x: fp32 [B, J], rows ld >= J elements apart, any 4-byte-aligned base; gamma / beta / running
 // statistics fp32 [J]; part: fp64 [jm_bn_chunks(B), 2, J] workspace; -1 bad argument, -2 failed launch)
 // row chunks of a batch (= rows of part), rows per chunk, columns per workgroup

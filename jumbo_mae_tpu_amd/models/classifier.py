@@ -64,12 +64,48 @@ class FinetuneModel:
         self.criterion = CRITERION_COLLECTION[criterion]
         self.criterion_name = criterion
         self.group = group
+        self.teacher: FinetuneModel | None = None  # attach_teacher
+        self.frozen = False
+
+    def freeze(self):
+        """Before ``to``: every segment frozen -- no gradient buffer is allocated and no op writes one
+        (a distillation teacher: outside the optimizer, the reducer and the EMA, which see the
+        student's store only)."""
+        assert not self.store.finalized
+        for s in self.store.segments:
+            s.trainable = False
+        self.frozen = True
+        return self
 
     def to(self, device, compute_dtype=torch.float32, seed: int = 0):
         g = torch.Generator(device=device).manual_seed(seed)
-        self.store.finalize(device, compute_dtype, g)
+        self.store.finalize(device, compute_dtype, g, with_grad=not self.frozen)
         self.head.init_stats(device)
         return self
+
+    def attach_teacher(self, teacher: "FinetuneModel", alpha: float = 0.5, temperature: float = 1.0,
+                       mode: str = "soft") -> None:
+        """Distillation: ``forward(det=False)`` then returns ``(1 - alpha) * base + alpha * mean kd`` with
+        ``kd`` = ``Fn.kd_loss`` of the student's logits against those of ``teacher`` (a frozen
+        FinetuneModel without BatchNorm head, dropout, droppath or Mixup, run on the same mixed patch
+        rows under ``no_grad``).  ``evaluate`` stays the student alone."""
+        tc, sc = teacher.cfg, self.cfg
+        if not (teacher.frozen and teacher.store.finalized and teacher.store.num_params(True) == 0):
+            raise ValueError("the teacher must be frozen (FinetuneModel.freeze) and on its device")
+        if tc.linear_probing or tc.batch_norm or tc.dropout or tc.droppath or teacher.mixup.active:
+            raise ValueError("the teacher runs without BatchNorm head, dropout, droppath and Mixup")
+        for k in ("patch_size", "image_size", "labels"):
+            if getattr(tc, k) != getattr(sc, k):
+                raise ValueError(f"teacher {k} {getattr(tc, k)} != student {k} {getattr(sc, k)}")
+        if teacher.store.compute_dtype != self.store.compute_dtype or teacher.device != self.device:
+            raise ValueError("teacher and student must share the compute dtype and the device")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"distillation alpha {alpha}: expected 0 <= alpha <= 1")
+        if not temperature > 0.0:
+            raise ValueError(f"distillation temperature {temperature}: expected > 0")
+        if mode not in Fn.KD_MODES:
+            raise ValueError(f"distillation mode {mode!r}: expected one of {Fn.KD_MODES}")
+        self.teacher, self.kd_alpha, self.kd_temperature, self.kd_mode = teacher, float(alpha), float(temperature), mode
 
     @property
     def device(self):
@@ -117,14 +153,17 @@ class FinetuneModel:
     def logits(self, images_u8, labels=None, rngs=None, det=True, raw=False, plan=_DRAW):
         """(logits, mixed labels); ``raw``: the head's output in the compute dtype instead of fp32;
         ``plan``: as in ``patches``."""
-        B = images_u8.shape[0]
         rows, labels = self.patches(images_u8, labels, rngs, det, plan)
+        return self.logits_of_rows(rows, images_u8.shape[0], rngs, det, raw), labels
+
+    def logits_of_rows(self, rows, B, rngs=None, det=True, raw=False):
+        """Encoder + head on prepared patch rows (``patches``)."""
         if self.cfg.linear_probing:
             with torch.no_grad():
                 feats = self.features(rows, B, rngs, det)
         else:
             feats = self.features(rows, B, rngs, det)
-        return self.head(feats, det, self.group, raw), labels
+        return self.head(feats, det, self.group, raw)
 
     # ---------------------------------------------------------------- train / eval
     def _fused_loss(self, images_u8, labels) -> bool:
@@ -135,6 +174,8 @@ class FinetuneModel:
                 and P.hip(images_u8))
 
     def forward(self, images_u8, labels, rngs=None, det=False):
+        if self.teacher is not None and not det:
+            return self._forward_distill(images_u8, labels, rngs)
         if self._fused_loss(images_u8, labels):
             plan = self.step_plan(images_u8, rngs, det)
             logits, _ = self.logits(images_u8, None, rngs, det, raw=True, plan=plan)
@@ -148,6 +189,34 @@ class FinetuneModel:
         loss = self.criterion(logits, labels).mean()
         acc1, acc5 = self.accuracy(logits, labels)
         return {"loss": loss, "acc1": acc1.float().mean(), "acc5": acc5.float().mean()}
+
+    def _forward_distill(self, images_u8, labels, rngs):
+        """The train step with a teacher: one plan and one set of mixed patch rows feed both networks
+        (the teacher takes nothing from ``rngs``); the base loss is the one ``forward`` computes without
+        a teacher, on the same path (fused or dense)."""
+        B = images_u8.shape[0]
+        plan = self.step_plan(images_u8, rngs, False)
+        rows, _ = self.patches(images_u8, None, rngs, False, plan)
+        with torch.no_grad():
+            u = self.teacher.logits_of_rows(rows, B, None, True, raw=True)
+        if self._fused_loss(images_u8, labels):
+            z = self.logits_of_rows(rows, B, rngs, False, raw=True)
+            base, acc1, acc5 = Fn.cls_loss(z, labels, plan, self.label_smoothing, self.criterion_name)
+            base = base.mean()
+        else:
+            t = Mixup.mix_labels(smooth_labels(self._prep_labels(labels), self.label_smoothing), plan)
+            z = self.logits_of_rows(rows, B, rngs, False)
+            base = self.criterion(z, t).mean()
+            acc1, acc5 = self.accuracy(z, t)
+        a = self.kd_alpha
+        with torch.set_grad_enabled(a > 0.0):
+            kd, agree = Fn.kd_loss(z, u.to(z.dtype), self.kd_temperature, self.kd_mode)
+            kd = kd.mean()
+        # the end points are taken literally: alpha 0 is the base loss bit for bit (value and backward),
+        # alpha 1 trains on the teacher alone
+        loss = base if a == 0.0 else (kd if a == 1.0 else (1.0 - a) * base + a * kd)
+        return {"loss": loss, "acc1": acc1.float().mean(), "acc5": acc5.float().mean(), "cls_loss": base.detach(),
+                "kd_loss": kd.detach(), "kd_agree": agree.float().mean()}
 
     __call__ = forward
 

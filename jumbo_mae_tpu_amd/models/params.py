@@ -287,7 +287,10 @@ class ParamStore:
         """Elements up to the end of the last segment (the flat total adds alignment padding)."""
         return max((s.offset + s.numel for s in self.segments), default=0)
 
-    def finalize(self, device, compute_dtype=torch.float32, generator: torch.Generator | None = None) -> None:
+    def finalize(self, device, compute_dtype=torch.float32, generator: torch.Generator | None = None,
+                 with_grad: bool = True) -> None:
+        """``with_grad=False`` (a store whose every segment is frozen): no gradient buffer, ``grad`` stays None."""
+        assert with_grad or not any(s.trainable for s in self.segments), "a trainable segment needs the gradient buffer"
         q = TOTAL_ALIGN
         # a data-parallel world that does not divide 1680 (32, 64 ranks) still gets equal 64-aligned
         # ZeRO-1 shards: pad to lcm(TOTAL_ALIGN, world * ALIGN)
@@ -297,7 +300,7 @@ class ParamStore:
         self.total = (self.total + q - 1) // q * q
         self.compute_dtype = compute_dtype
         self.master = torch.zeros(self.total, dtype=torch.float32, device=device)
-        self.grad = torch.zeros(self.total, dtype=torch.float32, device=device)
+        self.grad = torch.zeros(self.total, dtype=torch.float32, device=device) if with_grad else None
         if compute_dtype == torch.float32:
             self.shadow = self.master
         else:

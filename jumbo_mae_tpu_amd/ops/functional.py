@@ -226,3 +226,93 @@ def cls_loss(logits: torch.Tensor, labels_int: torch.Tensor, plan: dict | None =
     loss, hit = _ClsLoss.apply(logits, labels_int.long().contiguous(), perm, w, float(smoothing),
                                0 if criterion == "ce" else 1)
     return loss, hit[:, 0], hit[:, 1]
+
+
+# ---------------------------------------------------------------- distillation loss + agreement
+KD_MODES = ("soft", "hard")
+
+
+def argmax_first(x: torch.Tensor) -> torch.Tensor:
+    """arg-max over the last dim, the lowest index among ties -- by construction, not by the backend's
+    tie rule."""
+    L = x.shape[-1]
+    idx = torch.arange(L, device=x.device).expand(x.shape)
+    return torch.where(x == x.max(-1, keepdim=True).values, idx, L).min(-1).values.clamp_(max=L - 1)
+
+
+class _KdSoftTorch(torch.autograd.Function):
+    """T^2 KL(softmax(u / T) || softmax(z / T)) per row with the gradient written out, T (p - q): the
+    autograd of the composition would leave T^2 q (sum q - 1) where p == q."""
+
+    @staticmethod
+    def forward(ctx, z, u, T: float):
+        lp, lq = torch.log_softmax(z / T, -1), torch.log_softmax(u / T, -1)
+        p, q = lp.exp(), lq.exp()
+        ctx.save_for_backward(p, q)
+        ctx.T = T
+        return (T * T) * (q * (lq - lp)).sum(-1)
+
+    @staticmethod
+    def backward(ctx, dkd):
+        p, q = ctx.saved_tensors
+        return dkd.unsqueeze(-1) * (ctx.T * (p - q)), None, None
+
+
+def kd_loss_torch(z: torch.Tensor, u: torch.Tensor, T: float = 1.0, mode: str = "soft"):
+    """(kd [B], agree [B] bool) of student logits ``z`` against teacher logits ``u`` ([B, L]):
+      soft  kd = T^2 sum_c q_c (log q_c - log p_c), q = softmax(u / T), p = softmax(z / T); d kd / d z = T (p - q);
+      hard  kd = -log softmax(z)_t, t = the teacher's arg-max (DeiT; T unused); d kd / d z = softmax(z) - onehot(t);
+      agree = the two arg-maxima coincide; every arg-max is the lowest index among ties.
+    ``u`` takes no gradient.  Runs in the logits' dtype (bf16 / fp16 logits in fp32).  The CPU path of
+    ``kd_loss``, and what defines the kernels' semantics."""
+    if mode not in KD_MODES:
+        raise KeyError(mode)
+    if not T > 0:
+        raise ValueError(f"distillation temperature {T}: expected > 0")
+    u = u.detach()
+    if z.dtype in (torch.bfloat16, torch.float16):
+        z, u = z.float(), u.float()
+    t = argmax_first(u)
+    agree = argmax_first(z.detach()) == t
+    if mode == "soft":
+        return _KdSoftTorch.apply(z, u, float(T)), agree
+    return -torch.log_softmax(z, -1).gather(1, t.view(-1, 1)).squeeze(1), agree
+
+
+class _KdLoss(torch.autograd.Function):
+    """z, u [B, L] (bf16 or fp32, unit column stride) -> per-row kd fp32 and the bool agreement
+    (csrc/distill.hip); the backward reads u in soft mode and the saved teacher arg-max in hard mode."""
+
+    @staticmethod
+    def forward(ctx, z, u, T: float, mode: int):
+        kd, agree, lse, t = P._ext.load().kd_loss_fwd(z, u, T, mode)
+        ctx.save_for_backward(z, u if mode == 0 else None, lse, t if mode == 1 else None)
+        ctx.T, ctx.mode = T, mode
+        ctx.mark_non_differentiable(agree)
+        return kd, agree
+
+    @staticmethod
+    def backward(ctx, dkd, _dagree):
+        z, u, lse, t = ctx.saved_tensors
+        dz = P._ext.load().kd_loss_bwd(dkd.float().contiguous(), z, u, ctx.T, ctx.mode, lse, t)
+        return dz, None, None, None
+
+
+def _rows_ok(x: torch.Tensor) -> bool:
+    return x.stride(-1) == 1 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1])
+
+
+def kd_loss(z: torch.Tensor, u: torch.Tensor, T: float = 1.0, mode: str = "soft"):
+    """(kd [B] fp32, agree [B] bool) as ``kd_loss_torch`` defines them.  On the GPU one fused kernel each
+    way (u and the agreement carry no gradient); on the CPU, or with ``prims._KD_OURS`` off, the torch
+    composition."""
+    if not (P._KD_OURS and P.hip(z)):
+        return kd_loss_torch(z, u, T, mode)
+    if mode not in KD_MODES:
+        raise KeyError(mode)
+    if z.shape != u.shape or z.dtype != u.dtype:
+        raise ValueError(f"kd_loss: student {tuple(z.shape)} {z.dtype} against teacher {tuple(u.shape)} {u.dtype}")
+    z = z if _rows_ok(z) else z.contiguous()  # strided columns or overlapping rows (an expanded batch)
+    u = u.detach()
+    u = u if _rows_ok(u) else u.contiguous()
+    return _KdLoss.apply(z, u, float(T), KD_MODES.index(mode))

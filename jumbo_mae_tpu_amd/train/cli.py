@@ -4,7 +4,8 @@ Reference: /root/reference/src/main_pretrain.py:97-167 and main_finetune.py:97-1
 underscore spelling of ``--image_mask_ratio`` and the seeds defaulting to ``random.randint`` at
 parse time).  Additions (all optional, defaults keep reference behaviour): ``--resume``,
 ``--save-interval``, ``--mask-mode``, ``--compute-dtype``, ``--bucket-mb``, ``--device``,
-``--log-norms``, ``--ema-decay`` (``main_finetune`` only).
+``--log-norms``, ``--ema-decay`` and the distillation flags ``--teacher-*`` / ``--distill-*``
+(``main_finetune`` only).
 Flags the reference accepts but ignores (``--pooling``, ``--dec-posemb``, ``--label-mapping``,
 ``--ipaddr``, ``--hostname``; quirk Q10) are accepted and recorded.
 """
@@ -194,6 +195,23 @@ def finetune_parser() -> argparse.ArgumentParser:
                           "updated after every optimizer step: every evaluation also runs with the averaged weights "
                           "(val/ema_loss, val/ema_acc1, val/ema_acc5) and the best of them is written to "
                           "{name}-ema-best.msgpack; 0 <= D < 1, 0 = off")
+    ext.add_argument("--teacher-ckpt", default="",
+                     help="distillation: a finetune params checkpoint ({name}-best / -last / -ema-best .msgpack of this "
+                          "framework or of the reference) loaded into a frozen teacher; the train loss becomes "
+                          "(1 - alpha) * loss + alpha * kd and train/cls_loss, train/kd_loss, train/kd_agree are logged; "
+                          "the first evaluation also reports val/teacher_acc1 and val/teacher_loss; empty = off")
+    ext.add_argument("--teacher-layers", type=int, default=None, help="teacher depth (default: --layers)")
+    ext.add_argument("--teacher-dim", type=int, default=None, help="teacher width (default: --dim)")
+    ext.add_argument("--teacher-heads", type=int, default=None, help="teacher heads (default: --heads)")
+    ext.add_argument("--teacher-layerscale", action="store_true", default=False)
+    ext.add_argument("--distill-alpha", type=_distill_alpha, default=0.5,
+                     help="weight of the distillation term, 0 <= alpha <= 1 (0: the loss without a teacher, bit for "
+                          "bit; 1: the teacher alone)")
+    ext.add_argument("--distill-temperature", type=_distill_temperature, default=1.0,
+                     help="soft mode: T > 0 of kd = T^2 KL(softmax(teacher / T) || softmax(student / T))")
+    ext.add_argument("--distill-mode", default="soft", choices=["soft", "hard"],
+                     help="soft: temperature-scaled KL to the teacher's distribution; hard (DeiT): cross-entropy "
+                          "against the teacher's arg-max class")
     return p
 
 
@@ -202,3 +220,17 @@ def _ema_decay(v: str) -> float:
     if not 0.0 <= d < 1.0:
         raise argparse.ArgumentTypeError(f"--ema-decay {v}: expected 0 <= D < 1")
     return d
+
+
+def _distill_alpha(v: str) -> float:
+    a = float(v)
+    if not 0.0 <= a <= 1.0:
+        raise argparse.ArgumentTypeError(f"--distill-alpha {v}: expected 0 <= alpha <= 1")
+    return a
+
+
+def _distill_temperature(v: str) -> float:
+    t = float(v)
+    if not 0.0 < t < float("inf"):
+        raise argparse.ArgumentTypeError(f"--distill-temperature {v}: expected T > 0")
+    return t

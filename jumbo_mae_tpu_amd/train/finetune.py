@@ -16,7 +16,10 @@ Parity: /root/reference/src/main_finetune.py:37-94 and create_train_state
   * ``--attn-stats N`` (extension): at every evaluation rank 0 logs the per-layer attention entropy,
     largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py);
   * ``--attn-maps N`` (extension): at every evaluation rank 0 writes the CLS attention maps of the first N
-    validation images as a PNG panel and logs their entropy and CLS mass (ops/attn_maps.py).
+    validation images as a PNG panel and logs their entropy and CLS mass (ops/attn_maps.py);
+  * ``--teacher-ckpt URL`` (extension): distillation against a frozen finetuned teacher (``build_teacher``,
+    ``FinetuneModel.attach_teacher``, ops/functional.py ``kd_loss``): train/cls_loss, train/kd_loss and
+    train/kd_agree are logged and the first evaluation also runs with the teacher (val/teacher_*).
 """
 
 from __future__ import annotations
@@ -25,7 +28,7 @@ import time
 
 import torch
 
-from ..ckpt.checkpoint import load_pretrained_params, save_params
+from ..ckpt.checkpoint import load_params, load_pretrained_params, save_params
 from ..config import ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.classifier import FinetuneModel
@@ -50,6 +53,42 @@ def build_model(args, device, dtype, rank: int = 0) -> FinetuneModel:
                    linear_probing=linear, batch_norm=linear)
     mix = Mixup(args.mixup, args.cutmix, seed=args.mixup_seed * 1009 + rank)
     return FinetuneModel(vc, mix, args.label_smoothing, args.criterion).to(device, dtype, seed=args.init_seed)
+
+
+def build_teacher(args, device, dtype, log=print) -> FinetuneModel:
+    """--teacher-ckpt: the frozen distillation teacher -- the student's patch size, image size, labels and
+    position embedding; its own depth / width / heads / layerscale; no BatchNorm head, dropout, droppath
+    or Mixup -- with EVERY leaf (encoder and head) taken from the checkpoint: a missing leaf or a shape
+    mismatch is an error that names the leaf.  Every rank holds the whole teacher (rank 0's copy)."""
+    vc = ViTConfig(layers=args.teacher_layers or args.layers, dim=args.teacher_dim or args.dim,
+                   heads=args.teacher_heads or args.heads, labels=args.labels, layerscale=args.teacher_layerscale,
+                   patch_size=args.patch_size, image_size=args.image_size, posemb=args.posemb, pooling=args.pooling,
+                   dropout=0.0, droppath=0.0, grad_ckpt=False, image_mask_ratio=None, linear_probing=False,
+                   batch_norm=False)
+    teacher = FinetuneModel(vc, None, 0.0, args.criterion).freeze().to(device, dtype, seed=args.init_seed)
+    tree = load_params(args.teacher_ckpt)
+    if "model" not in tree and isinstance(tree.get("params"), dict):
+        tree = tree["params"]
+    try:
+        teacher.store.load_flax_tree(tree, strict=True)
+    except KeyError as e:
+        raise KeyError(f"--teacher-ckpt {args.teacher_ckpt}: no leaf {e.args[0]} (a finetune checkpoint with its "
+                       "head is needed; check --teacher-layers / --teacher-layerscale)") from None
+    except ValueError as e:
+        raise ValueError(f"--teacher-ckpt {args.teacher_ckpt}: {e} (check --teacher-dim / --teacher-heads / "
+                         "--labels)") from None
+    pdist.broadcast_(teacher.store.master)
+    teacher.store.sync_shadow()
+    log(f"Teacher weights are loaded from {args.teacher_ckpt}.")
+    return teacher
+
+
+def evaluate_teacher(teacher, loader, rngs, device) -> dict:
+    """The validation pass with the teacher (val/teacher_loss, val/teacher_acc1, val/teacher_acc5): how a
+    user sees that it loaded correctly.  As in ``evaluate_ema``, the default generator is put back."""
+    with torch.random.fork_rng(devices=[]):
+        res = evaluate(teacher, loader, rngs, device)
+    return {k.replace("val/", "val/teacher_"): v for k, v in res.items()}
 
 
 def evaluate(model, loader, rngs, device) -> dict:
@@ -98,6 +137,12 @@ def main(args) -> dict:
     pdist.broadcast_(model.store.master)
     model.store.sync_shadow()
     C.summarize_params(model.store, log)
+    teacher = None
+    if args.teacher_ckpt:  # rebuilt from the flag on --resume too: checkpoints hold the student only
+        teacher = build_teacher(args, device, dtype, log)
+        model.attach_teacher(teacher, args.distill_alpha, args.distill_temperature, args.distill_mode)
+        log(f"Distillation ({args.distill_mode}, alpha {args.distill_alpha:g}, T {args.distill_temperature:g}): "
+            f"student {model.store.num_params():,} parameters, teacher {teacher.store.num_params():,} (frozen)")
     if model.cfg.batch_norm:
         log("BatchNorm statistics are initialized.")
     peak = args.learning_rate * args.train_batch_size / 256 if args.optimizer == "lars" else args.learning_rate
@@ -129,6 +174,8 @@ def main(args) -> dict:
         if ema is not None:
             result.update(evaluate_ema(model, ema, valid_loader, rngs, device))
             result["val/ema_acc1/best"] = resumed.best("val/ema_acc1", 0.0)  # nothing is saved here
+        if teacher is not None:  # here and only here
+            result.update(evaluate_teacher(teacher, valid_loader, rngs, device))
         if args.attn_stats > 0 and info.is_main:
             result.update(C.evaluate_attn_stats(model, valid_loader, args, device, log))
         if args.attn_maps > 0 and info.is_main:
