@@ -1435,6 +1435,62 @@ torch::Tensor kd_loss_bwd(torch::Tensor dloss, torch::Tensor z, c10::optional<to
   return dz;
 }
 
+// ------------------------------------------------------------------------------ evaluation report
+static void check_eval_vec(const torch::Tensor& t, const torch::Tensor& like, torch::ScalarType dt, int64_t B,
+                           const char* what) {
+  TORCH_CHECK(t.device() == like.device() && t.scalar_type() == dt && t.dim() == 1 && t.size(0) == B &&
+                  t.is_contiguous(),
+              "eval_report: ", what, " must be a contiguous [B] vector of its dtype on the labels' device");
+}
+
+// [pred int32 [B], rank int32 [B], conf fp32 [B]]; padded (label -1) and non-finite rows: -1, -1, 0
+std::vector<torch::Tensor> eval_rows(torch::Tensor logits, torch::Tensor labels, int64_t mode) {
+  CHECK_CUDA(logits);
+  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16 || logits.scalar_type() == torch::kFloat32,
+              "eval_rows: logits must be bf16 or fp32");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "eval_rows: logits must be [B, L]");
+  TORCH_CHECK(logits.stride(1) == 1, "eval_rows: logits must have a unit column stride");
+  TORCH_CHECK(logits.size(0) == 1 || logits.stride(0) >= logits.size(1), "eval_rows: logits rows must not overlap");
+  TORCH_CHECK(logits.size(0) < INT_MAX && logits.size(1) < INT_MAX, "eval_rows: logits too large");
+  TORCH_CHECK(mode == 0 || mode == 1, "eval_rows: mode 0 (ce) or 1 (bce)");
+  const int64_t B = logits.size(0);
+  check_eval_vec(labels, logits, torch::kInt64, B, "labels");
+  auto pred = torch::empty({B}, logits.options().dtype(torch::kInt32));
+  auto rank = torch::empty({B}, logits.options().dtype(torch::kInt32));
+  auto conf = torch::empty({B}, logits.options().dtype(torch::kFloat32));
+  check_rc(jm_eval_rows(logits.data_ptr(), logits.scalar_type() == torch::kBFloat16, row_stride(logits),
+                        labels.data_ptr<int64_t>(), (int)mode, (int)B, (int)logits.size(1), pred.data_ptr<int>(),
+                        rank.data_ptr<int>(), conf.data_ptr<float>(), stream()),
+           "eval_rows");
+  return {pred, rank, conf};
+}
+
+int64_t eval_state_words(int64_t L, int64_t n_bins) {
+  TORCH_CHECK(L >= 1 && L < INT_MAX && n_bins >= 1 && n_bins <= JM_EVAL_MAX_BINS,
+              "eval_report: L >= 1 and 1 <= n_bins <= ", JM_EVAL_MAX_BINS);
+  return jm_eval_state_words((int)L, (int)n_bins);
+}
+
+// state (int64, eval_state_words(L, n_bins) words) += the batch
+void eval_accumulate(torch::Tensor labels, torch::Tensor pred, torch::Tensor rank, torch::Tensor conf, int64_t L,
+                     int64_t n_bins, torch::Tensor state) {
+  CHECK_CUDA(labels);
+  const int64_t B = labels.numel();
+  TORCH_CHECK(B >= 1 && B < INT_MAX, "eval_accumulate: 1 <= B < 2^31");
+  check_eval_vec(labels, labels, torch::kInt64, B, "labels");
+  check_eval_vec(pred, labels, torch::kInt32, B, "pred");
+  check_eval_vec(rank, labels, torch::kInt32, B, "rank");
+  check_eval_vec(conf, labels, torch::kFloat32, B, "conf");
+  const int64_t words = eval_state_words(L, n_bins);
+  TORCH_CHECK(state.device() == labels.device() && state.scalar_type() == torch::kInt64 && state.dim() == 1 &&
+                  state.is_contiguous() && state.size(0) == words,
+              "eval_accumulate: state must be int64 [", words, "] on the labels' device");
+  check_rc(jm_eval_accumulate(labels.data_ptr<int64_t>(), pred.data_ptr<int>(), rank.data_ptr<int>(),
+                              conf.data_ptr<float>(), (int)B, (int)L, (int)n_bins, state.data_ptr<int64_t>(),
+                              stream()),
+           "eval_accumulate");
+}
+
 // ------------------------------------------------------------------------------ batch norm
 // Argument checks of the bn_* entry points.  Dtypes, shapes and strides are checked before the
 // devices, and everything before any launch, so each message can be reached with CPU tensors.
@@ -1790,7 +1846,7 @@ py::dict debug_lines() {
       {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
       {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
       {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout},
-      {"distill", jm_debug_line_distill}};
+      {"distill", jm_debug_line_distill},     {"eval_report", jm_debug_line_eval_report}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1913,6 +1969,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "distillation loss -> (kd fp32 [B], agree bool [B], lse fp32 [B, 4], t int32 [B])");
   m.def("kd_loss_bwd", &kd_loss_bwd, py::arg("dloss"), py::arg("z"), py::arg("u"), py::arg("temperature"),
         py::arg("mode"), py::arg("lse"), py::arg("t") = py::none());
+  m.def("eval_rows", &eval_rows, py::arg("logits"), py::arg("labels"), py::arg("mode") = 0,
+        "evaluation report, per row -> (pred int32 [B], rank int32 [B], conf fp32 [B])");
+  m.def("eval_state_words", &eval_state_words, py::arg("L"), py::arg("n_bins"));
+  m.def("eval_accumulate", &eval_accumulate, py::arg("labels"), py::arg("pred"), py::arg("rank"), py::arg("conf"),
+        py::arg("L"), py::arg("n_bins"), py::arg("state"), "evaluation report: int64 state += the batch");
   m.def("knn_topk", &knn_topk, py::arg("q"), py::arg("bank"), py::arg("k"), py::arg("self_idx") = py::none(),
         py::arg("splits") = 0, py::arg("out_idx") = py::none(), py::arg("out_sim") = py::none(),
         "fused similarity + top-k -> (idx int32, sim fp32) [Nq, k], ties by ascending bank index");

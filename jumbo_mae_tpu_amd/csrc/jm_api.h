@@ -358,6 +358,26 @@ int jm_kd_loss_bwd(const void* z, long ldz, const void* u, long ldu, int bf16, d
                    const float* lse, const int* targ, const float* dloss, void* dz, long ldo, hipStream_t st);
 int jm_debug_line_distill();
 
+// ---- eval_report.hip (logits bf16 or fp32 [B, L], rows ld elements apart; labels int64 [B], -1 = padded row, other
+// out-of-range labels clamped; mode 0 = ce (softmax confidence), 1 = bce (sigmoid); -1 bad argument, -2 failed launch)
+// The int64 state, jm_eval_state_words(L, n_bins) words (-1: bad L / n_bins):
+//   [0] rows (neither padded nor non-finite)  [1] non-finite rows  [2] padded rows
+//   bins [n_bins, 3]: count, top-1 hits, sum of q = llrint(conf * 2^32)
+//   count [L], hit1 [L], hit5 [L] per true class, predicted [L] per predicted class
+//   confusion [L, L] (true x predicted), only while L <= JM_EVAL_MATRIX_MAX_L
+#define JM_EVAL_SCALARS 3
+#define JM_EVAL_MAX_BINS 64
+#define JM_EVAL_MATRIX_MAX_L 4096
+long jm_eval_state_words(int L, int n_bins);
+// pred int32 [B] = arg-max (lowest index on ties), rank int32 [B] = classes ahead of the label (strictly larger,
+// or equal at a lower index), conf fp32 [B] = probability of pred; padded and non-finite rows: -1, -1, 0
+int jm_eval_rows(const void* logits, int bf16, long ld, const int64_t* labels, int mode, int B, int L, int* pred,
+                 int* rank, float* conf, hipStream_t st);
+// state += this batch; no atomics, one writer per state word (L + n_bins + 1 workgroups)
+int jm_eval_accumulate(const int64_t* labels, const int* pred, const int* rank, const float* conf, int B, int L,
+                       int n_bins, int64_t* state, hipStream_t st);
+int jm_debug_line_eval_report();
+
 // ---- batchnorm.hip (x: fp32 [B, J], rows ld >= J elements apart, any 4-byte-aligned base; gamma / beta / running
 // statistics fp32 [J]; part: fp64 [jm_bn_chunks(B), 2, J] workspace; -1 bad argument, -2 failed launch)
 // row chunks of a batch (= rows of part), rows per chunk, columns per workgroup

@@ -254,11 +254,15 @@ class FinetuneModel:
         return AM.maps_and_mass(got, got.heads, self.cfg.num_cls_tokens, g, g, alpha, mode)
 
     @torch.no_grad()
-    def evaluate(self, images_u8, labels, rngs=None) -> dict:
-        """Sums over valid (label != -1) samples, like validation_step (finetuning.py:157-165)."""
+    def evaluate(self, images_u8, labels, rngs=None, report=None) -> dict:
+        """Sums over valid (label != -1) samples, like validation_step (finetuning.py:157-165).  ``report``
+        (ops/eval_report.py EvalReport) is fed the logits the loss reads and the labels as given; the sums
+        do not depend on it."""
         valid = (labels != -1)
         if self._fused_loss(images_u8, labels):
             logits, _ = self.logits(images_u8, None, rngs, det=True, raw=True)
+            if report is not None:
+                report.update(logits, labels)
             loss, acc1, acc5 = Fn.cls_loss(logits, torch.where(valid, labels, torch.zeros_like(labels)), None, 0.0,
                                            self.criterion_name)
             v = valid.float()
@@ -266,6 +270,8 @@ class FinetuneModel:
                     "num_samples": v.sum()}
         lab = self._prep_labels(torch.where(valid, labels, torch.zeros_like(labels)))
         logits, _ = self.logits(images_u8, lab, rngs, det=True)
+        if report is not None:
+            report.update(logits, labels)
         loss = self.criterion(logits, lab)
         acc1, acc5 = self.accuracy(logits, lab)
         v = valid.float()

@@ -157,6 +157,7 @@ _GEMM_MODE = "auto"  # auto | blas | ours (forward / dgrad routing)
 _DGRAD_OURS = True  # data-gradient GEMMs on the MFMA kernel
 _CLS_LOSS_OURS = True  # classification loss / accuracies on the fused kernels (csrc/loss.hip), else the torch composition
 _KD_OURS = True  # distillation loss / agreement on the fused kernels (csrc/distill.hip), else the torch composition
+_EVAL_REPORT_OURS = True  # evaluation report's per-row outputs and accumulation on the kernels (csrc/eval_report.hip), else the torch composition
 _BN_OURS = True  # linear-probe BatchNorm on the fused kernels (csrc/batchnorm.hip), else the torch composition
 _KNN_OURS = True  # k-NN monitor's top-k and vote on the fused kernels (csrc/knn.hip), else the torch composition
 _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc/optim.hip seg_stats), else the torch composition

@@ -4,8 +4,8 @@ Reference: /root/reference/src/main_pretrain.py:97-167 and main_finetune.py:97-1
 underscore spelling of ``--image_mask_ratio`` and the seeds defaulting to ``random.randint`` at
 parse time).  Additions (all optional, defaults keep reference behaviour): ``--resume``,
 ``--save-interval``, ``--mask-mode``, ``--compute-dtype``, ``--bucket-mb``, ``--device``,
-``--log-norms``, ``--ema-decay`` and the distillation flags ``--teacher-*`` / ``--distill-*``
-(``main_finetune`` only).
+``--log-norms``, ``--ema-decay``, the distillation flags ``--teacher-*`` / ``--distill-*`` and
+``--eval-report`` / ``--eval-report-bins`` (``main_finetune`` only).
 Flags the reference accepts but ignores (``--pooling``, ``--dec-posemb``, ``--label-mapping``,
 ``--ipaddr``, ``--hostname``; quirk Q10) are accepted and recorded.
 """
@@ -212,7 +212,22 @@ def finetune_parser() -> argparse.ArgumentParser:
     ext.add_argument("--distill-mode", default="soft", choices=["soft", "hard"],
                      help="soft: temperature-scaled KL to the teacher's distribution; hard (DeiT): cross-entropy "
                           "against the teacher's arg-max class")
+    ext.add_argument("--eval-report", action="store_true", default=False,
+                     help="every evaluation also reports val/mean_class_acc1, val/mean_class_acc5, "
+                          "val/worst_class_acc1, val/ece, val/mce, val/mean_conf, val/classes_seen and "
+                          "val/nonfinite_rows (with --ema-decay also val/ema_*), and rank 0 writes "
+                          "{name}-report-{step}.json (bins, per-class rows, most confused pairs) and, up to 4096 "
+                          "classes, the confusion matrix {name}-confusion-{step}.npy")
+    ext.add_argument("--eval-report-bins", type=_eval_report_bins, default=15,
+                     help="confidence bins of the calibration metrics (ECE / MCE), 1 <= N <= 64")
     return p
+
+
+def _eval_report_bins(v: str) -> int:
+    n = int(v)
+    if not 1 <= n <= 64:
+        raise argparse.ArgumentTypeError(f"--eval-report-bins {v}: expected 1 <= N <= 64")
+    return n
 
 
 def _ema_decay(v: str) -> float:

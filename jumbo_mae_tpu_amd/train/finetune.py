@@ -19,7 +19,10 @@ Parity: /root/reference/src/main_finetune.py:37-94 and create_train_state
     validation images as a PNG panel and logs their entropy and CLS mass (ops/attn_maps.py);
   * ``--teacher-ckpt URL`` (extension): distillation against a frozen finetuned teacher (``build_teacher``,
     ``FinetuneModel.attach_teacher``, ops/functional.py ``kd_loss``): train/cls_loss, train/kd_loss and
-    train/kd_agree are logged and the first evaluation also runs with the teacher (val/teacher_*).
+    train/kd_agree are logged and the first evaluation also runs with the teacher (val/teacher_*);
+  * ``--eval-report`` (extension): every evaluation also accumulates per-class accuracy, calibration bins and
+    the confusion matrix from its logits (ops/eval_report.py) -- val/mean_class_acc1, val/ece, ... -- and
+    rank 0 writes ``{name}-report-{step}.json`` and ``{name}-confusion-{step}.npy``.
 """
 
 from __future__ import annotations
@@ -32,8 +35,10 @@ from ..ckpt.checkpoint import load_params, load_pretrained_params, save_params
 from ..config import ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.classifier import FinetuneModel
+from ..ops.eval_report import EvalReport
 from ..optim.monitor import log_norms, make_monitor
 from ..parallel import dist as pdist
+from ..utils import gopen
 from ..utils.flops import finetune_fwd_flops_per_image
 from ..utils.mixup import Mixup
 from ..utils.trace import set_enabled as set_trace_ranges
@@ -91,11 +96,43 @@ def evaluate_teacher(teacher, loader, rngs, device) -> dict:
     return {k.replace("val/", "val/teacher_"): v for k, v in res.items()}
 
 
-def evaluate(model, loader, rngs, device) -> dict:
+def make_report(args, model, device):
+    """--eval-report: a fresh report for one validation pass, else None."""
+    if not args.eval_report:
+        return None
+    return EvalReport(model.cfg.labels, args.eval_report_bins, args.criterion, device)
+
+
+def finish_report(report, args, step: int, log, tag: str = "") -> dict:
+    """After the pass (COLLECTIVE): one int64 all-reduce, then rank 0 writes
+    ``{output_dir}/{name}-{tag}report-{step:07d}.json`` and, while the matrix is kept,
+    ``{name}-{tag}confusion-{step:07d}.npy``; returns the ``val/{tag}...`` metrics (``tag``: "" or "ema_")."""
+    import os
+
+    import numpy as np
+
+    report.all_reduce()
+    prefix = "val/" + tag
+    if pdist.info().is_main:
+        out = args.output_dir or "."
+        if gopen.is_local(out):
+            os.makedirs(out, exist_ok=True)
+            stem = os.path.join(out, f"{args.name or 'run'}-{tag.replace('_', '-')}")
+            with open(f"{stem}report-{step:07d}.json", "w") as f:
+                f.write(report.dumps(step, prefix))
+            cm = report.confusion()
+            if cm is not None:
+                np.save(f"{stem}confusion-{step:07d}.npy", cm)
+        else:
+            log(f"[eval] --eval-report: remote --output-dir {args.output_dir}, report files skipped")
+    return report.summary(prefix)
+
+
+def evaluate(model, loader, rngs, device, report=None) -> dict:
     rngs = rngs.fork()  # validation never advances the training streams
     sums = None
     for images, labels in C.DevicePrefetcher(loader, device):
-        m = model.evaluate(images, labels, rngs.as_dict())
+        m = model.evaluate(images, labels, rngs.as_dict(), **({} if report is None else {"report": report}))
         sums = m if sums is None else {k: sums[k] + m[k] for k in m}
     keys = ["loss", "acc1", "acc5", "num_samples"]
     packed = torch.stack([sums[k].float() for k in keys])
@@ -105,12 +142,12 @@ def evaluate(model, loader, rngs, device) -> dict:
     return {f"val/{k}": v / n for k, v in vals.items()}
 
 
-def evaluate_ema(model, ema, loader, rngs, device) -> dict:
+def evaluate_ema(model, ema, loader, rngs, device, report=None) -> dict:
     """The validation pass with the averaged weights swapped into the store (COLLECTIVE under ZeRO-1):
     val/ema_loss, val/ema_acc1, val/ema_acc5.  BatchNorm running statistics are the live ones.  A loader
     iterator seeds its workers from the default generator, which this second pass must not advance."""
     with ema.swapped(), torch.random.fork_rng(devices=[]):
-        res = evaluate(model, loader, rngs, device)
+        res = evaluate(model, loader, rngs, device, report)
     return {k.replace("val/", "val/ema_"): v for k, v in res.items()}
 
 
@@ -167,12 +204,25 @@ def main(args) -> dict:
                                                     device_augment=C.use_device_augment(args, device),
                                                     device_valid=C.use_device_valid(args, device))
     result = {}
+    step = start
+
+    def evaluate_with_report(model, ema, loader):
+        """``evaluate`` / ``evaluate_ema`` at the current step, with the --eval-report values merged in."""
+        report = make_report(args, model, device)
+        if ema is None:
+            res = evaluate(model, loader, rngs, device, report)
+        else:
+            res = evaluate_ema(model, ema, loader, rngs, device, report)
+        if report is not None:
+            res.update(finish_report(report, args, step, log, "" if ema is None else "ema_"))
+        return res
+
     logger = Logger(args.output_dir, args.name, args.project, vars(args), enabled=info.is_main,
                     use_wandb=False if args.log_file_only else None)
     if valid_loader is not None:  # SANITATION CHECK (main_finetune.py:53-54)
-        result.update(evaluate(model, valid_loader, rngs, device))
+        result.update(evaluate_with_report(model, None, valid_loader))
         if ema is not None:
-            result.update(evaluate_ema(model, ema, valid_loader, rngs, device))
+            result.update(evaluate_with_report(model, ema, valid_loader))
             result["val/ema_acc1/best"] = resumed.best("val/ema_acc1", 0.0)  # nothing is saved here
         if teacher is not None:  # here and only here
             result.update(evaluate_teacher(teacher, valid_loader, rngs, device))
@@ -220,13 +270,13 @@ def main(args) -> dict:
         # evaluation so that its sidecar carries the updated best metric
         per_rank = C.rank_states(rngs, model) if do_save else None
         if do_eval and valid_loader is not None:
-            res = evaluate(model, valid_loader, rngs, device)
+            res = evaluate_with_report(model, None, valid_loader)
             if res["val/acc1"] > max_acc1:  # identical on every rank (all-reduced)
                 max_acc1 = res["val/acc1"]
                 C.save_last(args, model, opt, step, rngs, extra(), postfix="best", per_rank=per_rank,
                             best=best(), ema=ema)
             if ema is not None:
-                res.update(evaluate_ema(model, ema, valid_loader, rngs, device))
+                res.update(evaluate_with_report(model, ema, valid_loader))
                 if res["val/ema_acc1"] > max_ema_acc1:  # identical on every rank (all-reduced)
                     max_ema_acc1 = res["val/ema_acc1"]
                     save_ema_best(args, model, ema)

@@ -9,7 +9,11 @@ evaluation (worker start-up, shard cache, kernel warm-up) and then ``--passes`` 
 evaluation is one pass over the shards, so its time includes refilling the workers' prefetch queues.
 The metrics of the two arms must be identical (the device path is bit-exact); that is asserted.
 
-    python tools/eval_rate.py [--workers 10,4] [--shards 40] [--per-shard 256] [--passes 3]
+    python tools/eval_rate.py [--workers 10,4] [--shards 40] [--per-shard 256] [--passes 3] [--eval-report]
+
+``--eval-report`` adds a third arm per worker count: the ``auto`` arm again with a fresh evaluation report
+(ops/eval_report.py) filled, all-reduced and summarized in every evaluation, as ``main_finetune
+--eval-report`` does (no files are written); its existing metrics must equal the other arms'.
 
 Prints one JSON line per (workers, arm) and a final summary line."""
 
@@ -39,10 +43,12 @@ def main():
     ap.add_argument("--workers", default="10,4")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--eval-report", action="store_true")
     a = ap.parse_args()
     from jumbo_mae_tpu_amd.data.loader import create_dataloaders
     from jumbo_mae_tpu_amd.train import common as C
     from jumbo_mae_tpu_amd.train.cli import finetune_parser
+    from jumbo_mae_tpu_amd.ops.eval_report import EvalReport
     from jumbo_mae_tpu_amd.train.finetune import build_model, evaluate
     from jumbo_mae_tpu_amd.utils.rng import RngStreams
 
@@ -53,7 +59,7 @@ def main():
     model, rows = None, []
     for nw in [int(x) for x in a.workers.split(",")]:
         metrics = {}
-        for mode in ("off", "auto"):
+        for mode, rep in [("off", False), ("auto", False)] + ([("auto", True)] if a.eval_report else []):
             args = finetune_parser().parse_args(FT + ["--valid-dataset-shards", spec, "--valid-batch-size", str(a.batch),
                                                       "--valid-loader-workers", str(nw), "--device-augment", mode])
             if model is None:
@@ -62,26 +68,39 @@ def main():
             dv = C.use_device_valid(args, device)
             assert dv == (mode == "auto"), (mode, dv)
             _, loader = create_dataloaders(args, device_valid=dv)
-            metrics[mode] = evaluate(model, loader, rngs, device)  # untimed: workers start, kernels warm
+
+            def run():
+                if not rep:
+                    return evaluate(model, loader, rngs, device)
+                report = EvalReport(model.cfg.labels, 15, args.criterion, device)
+                m = evaluate(model, loader, rngs, device, report)
+                report.all_reduce()
+                extra.update(report.summary())
+                return m
+
+            extra = {}
+            key = mode + ("+report" if rep else "")
+            metrics[key] = run()  # untimed: workers start, kernels warm
             times = []
             for _ in range(a.passes):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                m = evaluate(model, loader, rngs, device)
+                m = run()
                 torch.cuda.synchronize()
                 times.append(time.perf_counter() - t0)
-                assert m == metrics[mode], (m, metrics[mode])
+                assert m == metrics[key], (m, metrics[key])
             del loader
-            row = {"workers": nw, "device_augment": mode, "device_valid": dv, "images": images, "batch": a.batch,
+            row = {"workers": nw, "device_augment": mode, "device_valid": dv, "eval_report": rep, "images": images,
+                   "batch": a.batch, **({"report": extra} if rep else {}),
                    "passes_s": [round(t, 3) for t in times],
                    "images_per_sec": round(images / (sum(times) / len(times)), 1),
-                   "best_images_per_sec": round(images / min(times), 1), "val": metrics[mode],
+                   "best_images_per_sec": round(images / min(times), 1), "val": metrics[key],
                    "cpus": os.cpu_count()}
             rows.append(row)
             print(json.dumps(row), flush=True)
-        assert metrics["off"] == metrics["auto"], metrics  # bit-identical batches -> identical metrics
-    print(json.dumps({"summary": {f"{r['workers']}w_{r['device_augment']}": r["images_per_sec"] for r in rows}}),
-          flush=True)
+        assert all(m == metrics["off"] for m in metrics.values()), metrics  # bit-identical batches -> identical metrics
+    print(json.dumps({"summary": {f"{r['workers']}w_{r['device_augment']}" + ("+report" if r["eval_report"] else ""):
+                                  r["images_per_sec"] for r in rows}}), flush=True)
 
 
 if __name__ == "__main__":
