@@ -1834,6 +1834,92 @@ torch::Tensor attn_rollout_step(torch::Tensor qkv, int64_t heads, torch::Tensor 
   return out;
 }
 
+// ------------------------------------------------------------------------------ representation monitor
+// G fp64 [D, D] += x^T x, s fp64 [D] += column sums, over the rows with valid != 0 (all without valid); in place
+void feat_gram(torch::Tensor x, c10::optional<torch::Tensor> valid, torch::Tensor G, torch::Tensor s) {
+  TORCH_CHECK(x.is_cuda(), "feat_gram: x must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 && x.dim() == 2, "feat_gram: x must be fp32 [n, D]");
+  const int64_t n = x.size(0), D = x.size(1);
+  TORCH_CHECK(D >= 1 && D <= (1 << 20) && n < INT_MAX, "feat_gram: D must be in 1..2^20 and n below 2^31");
+  TORCH_CHECK(x.stride(1) == 1 || D == 1, "feat_gram: x must have a unit column stride");
+  TORCH_CHECK(n <= 1 || x.stride(0) >= D, "feat_gram: rows of x must not overlap");
+  TORCH_CHECK(G.scalar_type() == torch::kFloat64 && G.dim() == 2 && G.size(0) == D && G.size(1) == D &&
+                  G.is_contiguous() && G.device() == x.device(),
+              "feat_gram: G must be a contiguous fp64 [D, D] tensor on x's GPU");
+  TORCH_CHECK(s.scalar_type() == torch::kFloat64 && s.dim() == 1 && s.size(0) == D && s.is_contiguous() &&
+                  s.device() == x.device(),
+              "feat_gram: s must be a contiguous fp64 [D] tensor on x's GPU");
+  const uint8_t* vp = nullptr;
+  if (valid.has_value() && valid->defined()) {
+    const auto& v = *valid;
+    TORCH_CHECK((v.scalar_type() == torch::kUInt8 || v.scalar_type() == torch::kBool) && v.dim() == 1 &&
+                    v.size(0) == n && v.is_contiguous() && v.device() == x.device(),
+                "feat_gram: valid must be a contiguous uint8 or bool [n] tensor on x's GPU");
+    vp = reinterpret_cast<const uint8_t*>(v.data_ptr());
+  }
+  if (n == 0) return;
+  check_rc(jm_feat_gram(x.data_ptr<float>(), n > 1 ? x.stride(0) : D, vp, (int)n, (int)D, G.data_ptr<double>(),
+                        s.data_ptr<double>(), stream()),
+           "feat_gram");
+}
+
+// e fp64 [Nq] = per query the sum over valid bank rows j != self_idx of exp(-2 t (1 - q . bank_j))
+torch::Tensor feat_uniformity(torch::Tensor q, torch::Tensor bank, c10::optional<torch::Tensor> self_idx,
+                              c10::optional<torch::Tensor> bank_valid, double t, int64_t splits,
+                              c10::optional<torch::Tensor> out) {
+  const char* fn = "feat_uniformity";
+  for (const auto* p : {&q, &bank}) {
+    TORCH_CHECK(p->scalar_type() == torch::kBFloat16 && p->dim() == 2, fn, ": q and bank must be bf16 [N, D]");
+    TORCH_CHECK(p->size(1) >= 1 && p->stride(1) == 1, fn, ": q and bank must have a unit column stride");
+    TORCH_CHECK(p->size(0) <= 1 || p->stride(0) >= p->size(1), fn, ": rows must not overlap");
+    TORCH_CHECK(p->size(0) < INT_MAX && p->size(1) < INT_MAX, fn, ": q or bank too large");
+  }
+  TORCH_CHECK(q.size(1) == bank.size(1), fn, ": q and bank must have the same D");
+  TORCH_CHECK(q.size(1) % 32 == 0, fn, ": D must be a multiple of 32");
+  TORCH_CHECK(t > 0.0, fn, ": t must be positive");
+  TORCH_CHECK(splits >= 0 && splits <= 1024, fn, ": splits must be in 0..1024");
+  TORCH_CHECK(bank.size(0) >= 1, fn, ": the bank is empty");
+  TORCH_CHECK(bank.device() == q.device(), fn, ": q and bank must be on one device");
+  TORCH_CHECK(q.is_cuda(), fn, ": q must be a GPU tensor");
+  const int64_t Nq = q.size(0), Nb = bank.size(0);
+  const int* sp = nullptr;
+  if (self_idx.has_value() && self_idx->defined()) {
+    TORCH_CHECK(self_idx->scalar_type() == torch::kInt32 && self_idx->dim() == 1 && self_idx->size(0) == Nq &&
+                    self_idx->is_contiguous() && self_idx->device() == q.device(),
+                fn, ": self_idx must be int32 [Nq] on the inputs' device");
+    sp = self_idx->data_ptr<int>();
+  }
+  const uint8_t* vp = nullptr;
+  if (bank_valid.has_value() && bank_valid->defined()) {
+    const auto& v = *bank_valid;
+    TORCH_CHECK((v.scalar_type() == torch::kUInt8 || v.scalar_type() == torch::kBool) && v.dim() == 1 &&
+                    v.size(0) == Nb && v.is_contiguous() && v.device() == q.device(),
+                fn, ": bank_valid must be a contiguous uint8 or bool [Nb] tensor on the inputs' device");
+    vp = reinterpret_cast<const uint8_t*>(v.data_ptr());
+  }
+  const auto f64 = q.options().dtype(torch::kFloat64);
+  torch::Tensor e;
+  if (out.has_value() && out->defined()) {
+    e = *out;
+    TORCH_CHECK(e.scalar_type() == torch::kFloat64 && e.dim() == 1 && e.size(0) == Nq && e.is_contiguous() &&
+                    e.device() == q.device(),
+                fn, ": out must be a contiguous fp64 [Nq] tensor on the inputs' device");
+  } else {
+    e = torch::empty({Nq}, f64);
+  }
+  if (Nq == 0) return e;
+  const int64_t nseg = jm_feat_uniformity_segments((int)Nb);
+#ifdef JM_DEBUG
+  auto part = torch::zeros({nseg, Nq}, f64);  // a workgroup stopped by its guard adds nothing
+#else
+  auto part = torch::empty({nseg, Nq}, f64);
+#endif
+  check_rc(jm_feat_uniformity(q.data_ptr(), row_stride(q), bank.data_ptr(), row_stride(bank), sp, vp, (int)Nq, (int)Nb,
+                              (int)q.size(1), t, (int)splits, part.data_ptr<double>(), e.data_ptr<double>(), stream()),
+           fn);
+  return e;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1846,7 +1932,8 @@ py::dict debug_lines() {
       {"mae", jm_debug_line_mae},             {"optim", jm_debug_line_optim},
       {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
       {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout},
-      {"distill", jm_debug_line_distill},     {"eval_report", jm_debug_line_eval_report}};
+      {"distill", jm_debug_line_distill},     {"eval_report", jm_debug_line_eval_report},
+      {"feat_stats", jm_debug_line_feat_stats}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -1997,6 +2084,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows_out") = py::none(), "per-head attention statistics, fp64 [H, 6]");
   m.def("attn_rollout_step", &attn_rollout_step, py::arg("qkv"), py::arg("heads"), py::arg("r_in"), py::arg("alpha"),
         py::arg("out") = py::none(), "one attention-rollout step on fp32 rows [B, C, S] (C <= 8) -> fp32 [B, C, S]");
+  m.def("feat_gram", &feat_gram, py::arg("x"), py::arg("valid"), py::arg("G"), py::arg("s"),
+        "representation monitor: fp64 G [D, D] += x^T x, s [D] += column sums over the valid rows, in place");
+  m.def("feat_uniformity", &feat_uniformity, py::arg("q"), py::arg("bank"), py::arg("self_idx") = py::none(),
+        py::arg("bank_valid") = py::none(), py::arg("t") = 2.0, py::arg("splits") = 0, py::arg("out") = py::none(),
+        "representation monitor: fp64 [Nq] sums of exp(-2 t (1 - q . bank_j)) over the valid bank rows");
+  m.def("feat_uniformity_segments", &jm_feat_uniformity_segments, py::arg("Nb"),
+        "bank segments (rows of the workspace) of a feat_uniformity launch");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

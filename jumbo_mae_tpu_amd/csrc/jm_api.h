@@ -445,3 +445,22 @@ long jm_attn_rollout_ws(int B, int S, int H, int C);
 int jm_attn_rollout_step(const void* qkv, int B, int S, int H, int hd, const float* r_in, int C, double alpha,
                          float* r_out, float* ws, hipStream_t st);
 int jm_debug_line_attn_rollout();
+
+// ---- feat_stats.hip (representation monitor; -1 bad argument, -2 failed launch; no atomics, reruns bit-identical)
+// G fp64 [D, D] += sum over valid rows of x x^T, s fp64 [D] += sum over valid rows of x, in place.  x fp32 [n, D],
+// rows ldx >= D elements apart, any D in 1..2^20; valid bytes [n] or null (a row with valid == 0 is selected out
+// and may hold NaN).  Every product is the exact fp64 product of two fp32 values; an element is one chain in
+// ascending row order that starts from the state: two calls equal one call on the concatenated rows bit for bit
+// when the first call holds a multiple of 4 rows (the same MFMA steps run) or every partial sum is exact.  Only
+// tiles with i <= j are computed, the mirror is written: G stays symmetric bit for bit.
+int jm_feat_gram(const float* x, long ldx, const uint8_t* valid, int n, int D, double* G, double* s, hipStream_t st);
+// e fp64 [Nq]: e_i = sum over bank rows j with bank_valid[j] != 0 (null: all) and j != self_idx[i] (null or -1:
+// none) of exp(-2 t (1 - q_i . bank_j)); q / bank as for knn.hip (bf16, 16-byte aligned rows, D % 32 == 0), t > 0.
+// part: fp64 [jm_feat_uniformity_segments(Nb), Nq] workspace, one sum per bank segment of fixed size, added in
+// ascending order; splits (0 = one workgroup row per segment, else 1..1024) deals the segments to workgroups and
+// never shows in e.
+int jm_feat_uniformity_segments(int Nb);
+int jm_feat_uniformity(const void* q, long ldq, const void* bank, long ldb, const int* self_idx,
+                       const uint8_t* bank_valid, int Nq, int Nb, int D, double t, int splits, double* part, double* e,
+                       hipStream_t st);
+int jm_debug_line_feat_stats();

@@ -160,6 +160,7 @@ _KD_OURS = True  # distillation loss / agreement on the fused kernels (csrc/dist
 _EVAL_REPORT_OURS = True  # evaluation report's per-row outputs and accumulation on the kernels (csrc/eval_report.hip), else the torch composition
 _BN_OURS = True  # linear-probe BatchNorm on the fused kernels (csrc/batchnorm.hip), else the torch composition
 _KNN_OURS = True  # k-NN monitor's top-k and vote on the fused kernels (csrc/knn.hip), else the torch composition
+_FEAT_STATS_OURS = True  # representation monitor's Gram matrix and uniformity sums on the kernels (csrc/feat_stats.hip), else the torch composition
 _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc/optim.hip seg_stats), else the torch composition
 _ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused kernel (csrc/attn_stats.hip), else the torch composition
 _ATTN_MAPS_OURS = True  # attention maps' rollout step on the fused kernels (csrc/attn_rollout.hip), else the torch composition

@@ -173,6 +173,14 @@ def pretrain_parser() -> argparse.ArgumentParser:
                           "validation set (val/knn_acc1, val/knn_acc5; needs validation labels); 1..64, 0 = off")
     ext.add_argument("--knn-temperature", type=float, default=0.07,
                      help="temperature T of the k-NN vote: neighbour j weighs exp((sim_j - sim_0) / T)")
+    ext.add_argument("--feat-stats", action="store_true", default=False,
+                     help="at every evaluation: label-free statistics of the encoder features of the whole validation "
+                          "set (ops/feat_stats.py): val/feat_rankme (effective rank of the feature matrix), "
+                          "val/feat_pr (participation ratio of the covariance spectrum), val/feat_top1_var, "
+                          "val/feat_std, val/feat_rms_norm, val/feat_uniformity (log mean exp(-2 t (1 - cos)) over "
+                          "pairs of rows), val/feat_rows, val/feat_nonfinite; needs no validation labels")
+    ext.add_argument("--feat-uniformity-t", type=float, default=2.0,
+                     help="t of val/feat_uniformity (Wang & Isola use 2); must be positive")
     p.add_argument("--mask-mode", default="shared", choices=["shared", "per-sample"],
                    help="shared: one permutation per rank per step (reference, Q1)")
     return p

@@ -13,6 +13,8 @@ Parity: /root/reference/src/main_pretrain.py:37-94 and create_train_state
     (optim/monitor.py), written before the non-finite check so that an abort names its leaves;
   * ``--attn-stats N`` (extension): at every evaluation rank 0 logs the per-layer attention entropy,
     largest logit, largest probability and CLS mass of the first N validation images (ops/attn_stats.py);
+  * ``--feat-stats`` (extension): at every evaluation the label-free representation monitor -- effective rank,
+    participation ratio and uniformity of the encoder features of the whole validation set (ops/feat_stats.py);
   * ``--attn-maps N`` (extension): at every evaluation rank 0 writes the CLS attention maps of the first N
     validation images (unmasked) as a PNG panel and logs their entropy and CLS mass (ops/attn_maps.py).
 Launch: ``torchrun --nproc-per-node 8 src/main_pretrain.py <reference flags>``.
@@ -27,6 +29,7 @@ import torch
 from ..config import DecoderConfig, ViTConfig
 from ..data.loader import create_dataloaders
 from ..models.mae import PretrainModel
+from ..ops import feat_stats as feat_ops
 from ..ops import knn as knn_ops
 from ..optim.monitor import log_norms, make_monitor
 from ..parallel import dist as pdist
@@ -53,20 +56,29 @@ def build_model(args, device, dtype) -> PretrainModel:
                          mask_mode=getattr(args, "mask_mode", "shared")).to(device, dtype, seed=args.init_seed)
 
 
-def evaluate(model, loader, rngs, device, knn_k: int = 0, knn_T: float = 0.07, log=None) -> dict:
-    """val/loss, and with ``knn_k`` > 0 (--knn-k) the k-NN monitor's val/knn_acc1 / val/knn_acc5 from
-    the same pass over the validation shard (``knn_metrics``)."""
+def evaluate(model, loader, rngs, device, knn_k: int = 0, knn_T: float = 0.07, log=None, feat_stats: bool = False,
+             feat_t: float = 2.0) -> dict:
+    """val/loss, with ``knn_k`` > 0 (--knn-k) the k-NN monitor's val/knn_acc1 / val/knn_acc5 and with
+    ``feat_stats`` (--feat-stats) the representation monitor's val/feat_* from the same pass over the
+    validation shard (``knn_metrics``, ``FeatMonitor``); the features are extracted once for both."""
     rngs = rngs.fork()  # validation never advances the training streams
     sums = None
     feats, labs = [], []
+    monitor = FeatMonitor(feat_t) if feat_stats else None
     for batch in C.DevicePrefetcher(loader, device):
         images, labels = batch if isinstance(batch, (list, tuple)) else (batch, None)
         valid = (labels != -1) if labels is not None else None
         m = model.evaluate(images, valid, rngs.as_dict())
         sums = m if sums is None else {k: sums[k] + m[k] for k in m}
-        if knn_k > 0 and labels is not None:  # deterministic, no random stream: the loss above is unchanged
-            feats.append(knn_ops.normalize_features(model.features(images)))
-            labs.append(labels.to(torch.int64))
+        knn = knn_k > 0 and labels is not None
+        if knn or monitor is not None:  # deterministic, no random stream: the loss above is unchanged
+            f = model.features(images)
+            rows = knn_ops.normalize_features(f)
+            if knn:
+                feats.append(rows)
+                labs.append(labels.to(torch.int64))
+            if monitor is not None:
+                monitor.update(f, rows, valid)
     packed = torch.stack([sums["loss"], sums["num_samples"]]).float()
     pdist.all_reduce_sum_(packed)
     loss, n = packed.tolist()
@@ -76,42 +88,114 @@ def evaluate(model, loader, rngs, device, knn_k: int = 0, knn_T: float = 0.07, l
             out.update(knn_metrics(torch.cat(feats), torch.cat(labs), knn_k, knn_T))
         elif log is not None:
             log("[eval] --knn-k: the validation loader yields no labels, k-NN monitor skipped")
+    if monitor is not None:
+        out.update(monitor.finish())
     return out
+
+
+def gather_rows(feats: torch.Tensor, tags: torch.Tensor, pad: int):
+    """All-gather of this rank's rows ``feats`` [n, D] and their int64 ``tags`` [n], each shard padded
+    to the longest one with zero rows tagged ``pad`` (collective).  Returns (bank, bank_tags,
+    self_idx): the gathered rows in rank order and the bank index of each of this rank's own rows.
+    One process: the inputs themselves."""
+    import torch.distributed as dist
+
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    n = feats.shape[0]
+    self_idx = torch.arange(n, device=feats.device)
+    if world == 1:
+        return feats, tags, self_idx
+    rank = dist.get_rank()
+    longest = torch.tensor([n], dtype=torch.int64, device=feats.device)
+    dist.all_reduce(longest, op=dist.ReduceOp.MAX)
+    L = int(longest.item())
+    f = torch.zeros(L, feats.shape[1], dtype=feats.dtype, device=feats.device)
+    y = torch.full((L,), pad, dtype=torch.int64, device=feats.device)
+    f[:n], y[:n] = feats, tags
+    fw = f.view(torch.uint8)  # the bytes: every backend gathers uint8
+    gf = torch.empty(world * L, fw.shape[1], dtype=torch.uint8, device=feats.device)
+    gy = torch.empty(world * L, dtype=torch.int64, device=feats.device)
+    dist.all_gather(list(gf.chunk(world)), fw)  # the chunks are views: gathered in place, in rank order
+    dist.all_gather(list(gy.chunk(world)), y)
+    return gf.view(feats.dtype), gy, self_idx + rank * L
 
 
 def knn_metrics(feats: torch.Tensor, labels: torch.Tensor, k: int, T: float) -> dict:
     """Leave-one-out weighted k-NN accuracy over the whole validation set (collective).
 
     ``feats`` [n, D] bf16 normalised / ``labels`` [n] (-1 = padding) are this rank's shard.  The
-    ranks all-gather both, padded to the longest shard with label -1; each rank classifies its
-    own rows against the gathered bank, leaving out the row itself by its global index; hit sums
-    and the count travel in one packed all-reduce."""
-    import torch.distributed as dist
-
-    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-    n = feats.shape[0]
-    self_idx = torch.arange(n, device=feats.device)
-    bank, bank_labels = feats, labels
-    if world > 1:
-        rank = dist.get_rank()
-        longest = torch.tensor([n], dtype=torch.int64, device=feats.device)
-        dist.all_reduce(longest, op=dist.ReduceOp.MAX)
-        L = int(longest.item())
-        f = torch.zeros(L, feats.shape[1], dtype=feats.dtype, device=feats.device)
-        y = torch.full((L,), -1, dtype=torch.int64, device=feats.device)
-        f[:n], y[:n] = feats, labels
-        fw = f.view(torch.uint8)  # the bytes: every backend gathers uint8
-        gf = torch.empty(world * L, fw.shape[1], dtype=torch.uint8, device=feats.device)
-        gy = torch.empty(world * L, dtype=torch.int64, device=feats.device)
-        dist.all_gather(list(gf.chunk(world)), fw)  # the chunks are views: gathered in place, in rank order
-        dist.all_gather(list(gy.chunk(world)), y)
-        bank, bank_labels = gf.view(feats.dtype), gy
-        self_idx = self_idx + rank * L
+    ranks all-gather both, padded to the longest shard with label -1 (``gather_rows``); each rank
+    classifies its own rows against the gathered bank, leaving out the row itself by its global index;
+    hit sums and the count travel in one packed all-reduce."""
+    bank, bank_labels, self_idx = gather_rows(feats, labels, -1)
     hit1, hit5 = knn_ops.knn_classify(feats, labels, k, T, bank, bank_labels, self_idx)
     packed = torch.stack([hit1.sum(), hit5.sum(), (labels != -1).sum()]).double()
     pdist.all_reduce_sum_(packed)
     h1, h5, cnt = packed.tolist()
     return {"val/knn_acc1": h1 / max(cnt, 1.0), "val/knn_acc5": h5 / max(cnt, 1.0)}
+
+
+class FeatMonitor:
+    """The representation monitor of one evaluation pass (--feat-stats): ``update`` per batch, then
+    ``finish`` (collective) returns the val/feat_* metrics of ops/feat_stats.py ``summary``.
+
+    A row counts when the loader does not mark it as padding (label -1; without labels every row
+    counts) and all of its features are finite; the others are kept out of the Gram state through
+    ``valid`` and out of the uniformity through ``bank_valid``, and the non-finite ones are counted."""
+
+    def __init__(self, t: float = 2.0):
+        self.t = float(t)
+        self.state = None
+        self.rows, self.valid = [], []
+        self.nonfinite = None
+
+    def update(self, f: torch.Tensor, rows: torch.Tensor | None = None, valid: torch.Tensor | None = None) -> None:
+        """``f`` fp32 [B, D] features, ``rows`` their ``normalize_features`` (computed when None),
+        ``valid`` bool [B] (None: every row)."""
+        if self.state is None:
+            self.state = feat_ops.new_state(f.shape[1], f.device)
+            self.nonfinite = torch.zeros(1, dtype=torch.float64, device=f.device)
+        real = valid.bool() if valid is not None else torch.ones(f.shape[0], dtype=torch.bool, device=f.device)
+        finite = feat_ops.finite_rows(f)
+        ok = real & finite
+        feat_ops.feat_gram(f, ok, self.state)
+        self.nonfinite += (real & ~finite).sum()
+        self.rows.append(knn_ops.normalize_features(f) if rows is None else rows)
+        self.valid.append(ok)
+
+    def finish(self) -> dict:
+        """G, s, n and the non-finite count are all-reduced in fp64; the bf16 rows and their validity
+        are all-gathered (``gather_rows``) and each rank sums e over its own rows against the gathered
+        bank; e_sum and pairs travel in one packed all-reduce.  Rank 0 alone runs ``summary`` (a copy of
+        G to the host and two eigvalsh calls) and broadcasts the few scalars: every rank returns the
+        same dict.  Every rank must have seen at least one batch."""
+        if self.state is None:
+            raise RuntimeError("FeatMonitor.finish: no batch was seen")
+        st = self.state
+        pdist.all_reduce_sum_(st["G"])
+        tail = torch.cat([st["s"], st["n"], self.nonfinite])
+        pdist.all_reduce_sum_(tail)
+        D = st["s"].shape[0]
+        st["s"], st["n"], self.nonfinite = tail[:D], tail[D:D + 1], tail[D + 1:]
+        rows, ok = torch.cat(self.rows), torch.cat(self.valid)
+        bank, bank_ok, self_idx = gather_rows(rows, ok.to(torch.int64), 0)
+        bank_ok = bank_ok != 0
+        e = feat_ops.feat_uniformity(rows, bank, self_idx, bank_ok, self.t)
+        total = bank_ok.sum().double()
+        packed = torch.stack([e[ok].sum(), ok.sum().double() * (total - 1.0)])
+        pdist.all_reduce_sum_(packed)
+        e_sum, pairs = packed.tolist()
+        keys = feat_ops.KEYS
+        vals = torch.zeros(2 * len(keys), dtype=torch.float64, device=packed.device)  # values, then presence
+        import torch.distributed as dist
+
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
+            out = feat_ops.summary(st["G"], st["s"], int(st["n"].item()), e_sum, pairs, int(self.nonfinite.item()))
+            vals = torch.tensor([out.get(k, 0.0) for k in keys] + [float(k in out) for k in keys],
+                                dtype=torch.float64, device=packed.device)
+        pdist.broadcast_(vals)
+        vals = vals.tolist()
+        return {k: v for k, v, have in zip(keys, vals, vals[len(keys):]) if have}
 
 
 first_images = C.first_images
@@ -156,6 +240,8 @@ def main(args) -> dict:
         knn_ops.check_k(args.knn_k)  # before any work: 1..64
         if not args.knn_temperature > 0:
             raise ValueError(f"--knn-temperature must be positive (got {args.knn_temperature})")
+    if args.feat_stats and not args.feat_uniformity_t > 0:  # before any work
+        raise ValueError(f"--feat-uniformity-t must be positive (got {args.feat_uniformity_t})")
     info = pdist.init_distributed(args.device)
     set_trace_ranges(args.trace_ranges)
     device = info.device
@@ -183,7 +269,8 @@ def main(args) -> dict:
     logger = Logger(args.output_dir, args.name, args.project, vars(args), enabled=info.is_main,
                     use_wandb=False if args.log_file_only else None)
     if valid_loader is not None:  # SANITATION CHECK (main_pretrain.py:53-54), skipped without a valid set (Q8)
-        result.update(evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log))
+        result.update(evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log,
+                               args.feat_stats, args.feat_uniformity_t))
         if args.recon_images > 0 and info.is_main:
             result.update(evaluate_recon(model, valid_loader, args, device, start, log))
         if args.attn_stats > 0 and info.is_main:
@@ -229,7 +316,8 @@ def main(args) -> dict:
         # evaluation so that its sidecar carries the updated best metric
         per_rank = C.rank_states(rngs, model) if do_save else None
         if do_eval and valid_loader is not None:
-            res = evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log)
+            res = evaluate(model, valid_loader, rngs, device, args.knn_k, args.knn_temperature, log,
+                           args.feat_stats, args.feat_uniformity_t)
             if res["val/loss"] < min_val_loss:  # identical on every rank (all-reduced)
                 min_val_loss = res["val/loss"]
                 C.save_last(args, model, opt, step, rngs, postfix="best", per_rank=per_rank,
