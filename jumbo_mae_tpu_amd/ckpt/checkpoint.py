@@ -131,6 +131,31 @@ def _resize_posemb(arr: np.ndarray, shape) -> np.ndarray:
     return t[0].permute(1, 2, 0).numpy()
 
 
+POSEMB_MISMATCH = ("the checkpoint and the model were built with different position embeddings: pass the --posemb "
+                   "(and, for rope, the --rope-theta) the checkpoint was trained with")
+
+
+def _posemb_kind(model_tree: dict):
+    """("rope", theta) | ("learnable", None) | ("none", None) of a ``model`` subtree: a rope model's tree has the
+    frozen marker ``embed/rope_theta`` and no ``embed/wpe``; a sincos2d tree has neither."""
+    embed = model_tree.get("embed", {})
+    if "rope_theta" in embed:
+        return "rope", float(np.asarray(embed["rope_theta"]).reshape(-1)[0])
+    return ("learnable" if "wpe" in embed else "none"), None
+
+
+def check_posemb(src: dict, dst: dict) -> None:
+    """Loading the ``model`` subtree ``src`` into a model whose fresh tree is ``dst``: a rotary model takes
+    only a rotary checkpoint of the same theta, and a rotary checkpoint goes only into a rotary model.
+    (A table-free sincos2d checkpoint into a learnable model stays allowed: the table keeps its init.)"""
+    (sk, st), (dk, dt) = _posemb_kind(src), _posemb_kind(dst)
+    if (sk == "rope") != (dk == "rope") or (sk == "rope" and abs(st - dt) > 1e-6 * abs(dt)):
+        def name(k, t):
+            return f"--posemb rope --rope-theta {t:g}" if k == "rope" else \
+                ("--posemb learnable" if k == "learnable" else "a table-free --posemb (sincos2d)")
+        raise ValueError(f"checkpoint of {name(sk, st)} into a model of {name(dk, dt)}: {POSEMB_MISMATCH}")
+
+
 def load_pretrained_params(url: str, params: dict, log=print) -> dict:
     """Merge the ``model`` subtree of a pretrained checkpoint into ``params`` (a Flax tree).
 
@@ -141,6 +166,7 @@ def load_pretrained_params(url: str, params: dict, log=print) -> dict:
     new = load_params(url)
     src = new.get("model", new)
     dst = params["model"]
+    check_posemb(src, dst)
     overlap = len(set(src).intersection(dst))
     log(f"[*] load pretrained params with overlap of {overlap}/{len(dst)}")
 

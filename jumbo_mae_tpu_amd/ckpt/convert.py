@@ -38,15 +38,20 @@ def flax_to_torch(params: dict, exclude_heads: bool = False, num_cls: int = 3, i
     cls = _t(m["cls_tokens"]) if "cls_tokens" in m else _t(m.get("embed", {}).get("cls_token", np.zeros((1, 1, D))))
     sd["cls_tokens"] = cls
     sd["cls_token"] = cls[:, :1]
-    if "wpe" in emb:
-        pos = _t(emb["wpe"])
-        g = pos.shape[0]
+    if "rope_theta" in emb:
+        # --posemb rope: nothing is added at the embedding, so there is no pos_embed; the marker leaf travels as it
+        # is (this project's own axial convention, ops/rope.py -- not that of timm's rope ViTs)
+        sd["rope_theta"] = _t(emb["rope_theta"])
     else:
-        k = emb["wte"]["kernel"]
-        g = image_size // k.shape[0]  # HWIO kernel: k.shape[0] is the patch size
-        pos = _sincos2d_np(g, g, D)
-    pos = pos.reshape(1, -1, D)
-    sd["pos_embed"] = np.concatenate([np.zeros((1, cls.shape[1], D), np.float32), pos], 1)
+        if "wpe" in emb:
+            pos = _t(emb["wpe"])
+            g = pos.shape[0]
+        else:
+            k = emb["wte"]["kernel"]
+            g = image_size // k.shape[0]  # HWIO kernel: k.shape[0] is the patch size
+            pos = _sincos2d_np(g, g, D)
+        pos = pos.reshape(1, -1, D)
+        sd["pos_embed"] = np.concatenate([np.zeros((1, cls.shape[1], D), np.float32), pos], 1)
     sd["patch_embed.proj.weight"] = _t(emb["wte"]["kernel"]).transpose(3, 2, 0, 1).copy()
     sd["patch_embed.proj.bias"] = _t(emb["wte"]["bias"])
     if "norm" in m:
@@ -118,6 +123,8 @@ def torch_to_flax(sd: dict, num_heads: int, exclude_heads: bool = False, learnab
             pos = pos[:, 1:]
         if learnable_posemb:
             m["embed"]["wpe"] = pos.reshape(g, g, D)
+    if "rope_theta" in sd:
+        m["embed"]["rope_theta"] = sd["rope_theta"].reshape(1)
     m["cls_tokens"] = cls
     if "norm.weight" in sd:
         m["norm"] = {"scale": sd["norm.weight"], "bias": sd["norm.bias"]}

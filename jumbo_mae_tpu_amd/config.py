@@ -24,7 +24,8 @@ class ViTConfig:
 
     patch_size: int = 16
     image_size: int = 224
-    posemb: Literal["learnable", "sincos2d"] = "learnable"
+    posemb: Literal["learnable", "sincos2d", "rope"] = "learnable"
+    rope_theta: float = 100.0  # base of the axial rotary frequencies (posemb == "rope", ops/rope.py)
     pooling: Literal["cls", "gap"] = "cls"  # accepted for CLI parity, unused (modeling.py:272)
 
     dropout: float = 0.0

@@ -1920,6 +1920,46 @@ torch::Tensor feat_uniformity(torch::Tensor q, torch::Tensor bank, c10::optional
   return e;
 }
 
+// ------------------------------------------------------------------------------ rotary position embedding
+// rotates q and k of the patch rows of qkv [B, S, 3 heads hd] in place (rope.hip); returns qkv
+torch::Tensor rope_apply(torch::Tensor qkv, int64_t heads, int64_t n_cls, int64_t gw, torch::Tensor table,
+                         c10::optional<torch::Tensor> pos, bool inverse) {
+  const char* fn = "rope_apply";
+  TORCH_CHECK(qkv.is_cuda(), fn, ": qkv must be a GPU tensor");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), fn, ": qkv must be a contiguous [B, S, 3 heads hd] tensor");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 || qkv.scalar_type() == torch::kFloat32, fn,
+              ": qkv must be bf16 or fp32");
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && W % (3 * heads) == 0, fn, ": the last dim must be 3 heads hd");
+  const int64_t hd = W / (3 * heads);
+  TORCH_CHECK(hd % 16 == 0, fn, ": hd must be a multiple of 16");
+  TORCH_CHECK(n_cls >= 0 && n_cls <= S && gw >= 1, fn, ": n_cls must be in 0..S and gw positive");
+  TORCH_CHECK(B * S < INT_MAX && W < INT_MAX, fn, ": qkv too large");
+  TORCH_CHECK(table.scalar_type() == torch::kFloat32 && table.dim() == 3 && table.size(0) >= 1 &&
+                  table.size(1) == hd / 4 && table.size(2) == 2 && table.is_contiguous() &&
+                  table.device() == qkv.device(),
+              fn, ": table must be a contiguous fp32 [G, hd / 4, 2] tensor on qkv's device");
+  const int64_t G = table.size(0), Sp = S - n_cls;
+  TORCH_CHECK(G * gw < INT_MAX, fn, ": table too large");
+  const int* pp = nullptr;
+  long pb = 0;
+  if (pos.has_value() && pos->defined()) {
+    const auto& p = *pos;
+    TORCH_CHECK(p.scalar_type() == torch::kInt32 && p.is_contiguous() && p.device() == qkv.device() &&
+                    ((p.dim() == 1 && p.size(0) == Sp) || (p.dim() == 2 && p.size(0) == B && p.size(1) == Sp)),
+                fn, ": pos must be a contiguous int32 [S - n_cls] or [B, S - n_cls] tensor on qkv's device");
+    pp = p.data_ptr<int>();
+    pb = p.dim() == 2 ? (long)Sp : 0;
+  } else {
+    TORCH_CHECK(Sp <= G * gw, fn, ": the table covers fewer positions than the sequence has patch rows");
+  }
+  if (B == 0 || Sp == 0) return qkv;
+  check_rc(jm_rope_apply(qkv.data_ptr(), qkv.scalar_type() == torch::kBFloat16, (int)B, (int)S, (int)heads, (int)hd,
+                         (int)n_cls, (int)gw, table.data_ptr<float>(), (int)G, pp, pb, inverse ? 1 : 0, stream()),
+           fn);
+  return qkv;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1933,7 +1973,7 @@ py::dict debug_lines() {
       {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
       {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout},
       {"distill", jm_debug_line_distill},     {"eval_report", jm_debug_line_eval_report},
-      {"feat_stats", jm_debug_line_feat_stats}};
+      {"feat_stats", jm_debug_line_feat_stats}, {"rope", jm_debug_line_rope}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -2091,6 +2131,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "representation monitor: fp64 [Nq] sums of exp(-2 t (1 - q . bank_j)) over the valid bank rows");
   m.def("feat_uniformity_segments", &jm_feat_uniformity_segments, py::arg("Nb"),
         "bank segments (rows of the workspace) of a feat_uniformity launch");
+  m.def("rope_apply", &rope_apply, py::arg("qkv"), py::arg("heads"), py::arg("n_cls"), py::arg("gw"), py::arg("table"),
+        py::arg("pos") = py::none(), py::arg("inverse") = false,
+        "axial 2-D rotary embedding of q and k of the patch rows of qkv [B, S, 3 heads hd], in place");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

@@ -464,3 +464,14 @@ int jm_feat_uniformity(const void* q, long ldq, const void* bank, long ldb, cons
                        const uint8_t* bank_valid, int Nq, int Nb, int D, double t, int splits, double* part, double* e,
                        hipStream_t st);
 int jm_debug_line_feat_stats();
+
+// ---- rope.hip (axial 2-D rotary position embedding, ops/rope.py; -1 bad argument, -2 failed launch; no atomics,
+// reruns bit-identical)
+// rotates, in place, the q and k thirds of the patch rows t >= n_cls of the contiguous bf16 or fp32 qkv
+// [B, S, 3, heads, hd], hd % 16 == 0; the v third and the first n_cls rows of every sequence are neither read nor
+// written.  Row t has patch index p = t - n_cls (pos null) or pos[b * posB + t - n_cls] (int32; posB 0 = one shared
+// list) at coordinates (p / gw, p % gw); table fp32 [G, hd / 4, 2] = (cos, sin) of coord * theta^(-i / (hd / 4)),
+// 0 <= p < G gw (the debug build soft-checks it; p is clamped into the table).  inverse: the transpose (sin negated)
+int jm_rope_apply(void* qkv, int bf16, int B, int S, int heads, int hd, int n_cls, int gw, const float* table, int G,
+                  const int* pos, long posB, int inverse, hipStream_t st);
+int jm_debug_line_rope();

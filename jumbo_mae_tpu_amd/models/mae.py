@@ -80,7 +80,7 @@ class PretrainModel:
         rows = mae_ops.kept_patches(images_u8, ids_keep, cfg.patch_size, self.store.compute_dtype)
         drop = rngs.get("dropout")
         x = self.encoder.embed_rows(rows, ids_keep, B)
-        x = self.encoder.blocks(x, drop, det=enc_det)
+        x = self.encoder.blocks(x, drop, det=enc_det, ids=ids_keep)
         h = self.encoder.norm(x)  # [B*(C+K), D]
         y = self.decoder_proj(h).view(B, C + K, -1)
         dec_in = mae_ops.unshuffle_fused(y, self.mask_token, ids_restore, self.decoder.posemb_table(y.device), C)

@@ -39,10 +39,33 @@ def _dense_general_in(x, p):  # (..., D) @ (D, H, hd) -> (..., H, hd)
     return torch.einsum("...d,dhk->...hk", x, p["kernel"]) + p["bias"]
 
 
-def _attention(x, p, heads):
+def rope_cos_sin(pidx, gw, hd, theta, dtype):
+    """(cos, sin) [.., S_p, 1, hd/2] of the axial rotary embedding (ops/rope.py) at the patch indices ``pidx``
+    [.., S_p]: channel pairs [0, hd/4) turn by y = p // gw, pairs [hd/4, hd/2) by x = p % gw, pair i by
+    coord * theta^(-i / (hd/4)); the angles' cos / sin are rounded through fp32 like the model's table."""
+    n = hd // 4
+    freq = float(theta) ** (-torch.arange(n, dtype=torch.float64, device=pidx.device) / n)
+    yx = torch.stack([pidx // gw, pidx % gw], -1).to(torch.float64)  # [.., S_p, 2]
+    ang = (yx[..., None] * freq).flatten(-2)  # [.., S_p, hd/2]: the y pairs, then the x pairs
+    return ang.cos().float().to(dtype)[..., None, :], ang.sin().float().to(dtype)[..., None, :]
+
+
+def _rotate(t, cs, C):
+    """q or k [B, S, H, hd] with the pairs (2i, 2i + 1) of the rows t >= C turned by ``cs`` = (cos, sin)."""
+    c, s = cs
+    pt = t[:, C:]
+    x0, x1 = pt[..., 0::2], pt[..., 1::2]
+    rot = torch.stack([x0 * c - x1 * s, x1 * c + x0 * s], -1).flatten(-2)
+    return torch.cat([t[:, :C], rot], 1)
+
+
+def _attention(x, p, heads, rope=None):
+    """``rope`` = ((cos, sin), C): rotary embedding of q and k on the rows t >= C, or None."""
     q = _dense_general_in(x, p["wq"])
     k = _dense_general_in(x, p["wk"])
     v = _dense_general_in(x, p["wv"])
+    if rope is not None:
+        q, k = _rotate(q, *rope), _rotate(k, *rope)
     hd = q.shape[-1]
     z = torch.einsum("bqhd,bkhd->bhqk", q / hd ** 0.5, k)
     z = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(z, -1), v)
@@ -57,8 +80,8 @@ def _scale(p, name):
     return p[name] if name in p else 1.0
 
 
-def jumbo_layer(x, p, jumbo, heads, C=3):
-    x = x + _scale(p, "scale1") * _attention(_ln(x, p["norm1"]), p["attn"], heads)
+def jumbo_layer(x, p, jumbo, heads, C=3, rope=None):
+    x = x + _scale(p, "scale1") * _attention(_ln(x, p["norm1"]), p["attn"], heads, rope)
     cls, pt = x[:, :C], x[:, C:]
     b = cls.shape[0]
     cc = cls.reshape(b, -1)
@@ -86,13 +109,13 @@ def patch_embed(images_nhwc, p, posemb, patch, dim):
     x = x.permute(0, 2, 3, 1)  # B h w D
     if "wpe" in p:
         x = x + p["wpe"]
-    else:
+    elif posemb is not None:  # (None: rope, nothing is added at the embedding)
         x = x + posemb.to(x.device, x.dtype)
     return x.reshape(x.shape[0], -1, dim)
 
 
 def mae_loss(params, images_u8, noise, *, layers, dim, heads, dec_layers, dec_dim, dec_heads,
-             patch, mask_ratio, norm_pix_loss=False, posemb="sincos2d", C=3, dtype=torch.float64):
+             patch, mask_ratio, norm_pix_loss=False, posemb="sincos2d", C=3, dtype=torch.float64, rope_theta=100.0):
     """Reference PretrainModule.__call__ with a given masking noise (shape (N,) or (B,N)).  Runs on
     the device of ``images_u8`` in ``dtype`` (fp64 on the CPU for the parity tests; fp32 on the GPU
     as the reference of the ViT-L-width test)."""
@@ -115,8 +138,13 @@ def mae_loss(params, images_u8, noise, *, layers, dim, heads, dec_layers, dec_di
     if mask.dim() == 1:
         mask = mask.expand(B, N)
     x = torch.cat([cls, kept], 1)
+    rope = None
+    if posemb == "rope":  # a kept patch keeps its grid coordinate
+        rope = (rope_cos_sin(ids_shuffle[..., :keep], g, dim // heads, rope_theta, dtype), C)
+        if noise.dim() == 1:
+            rope = (tuple(t[None] for t in rope[0]), C)
     for i in range(layers):
-        x = jumbo_layer(x, m[f"layer_{i}"], m["jumbo_mlp"], heads, C)
+        x = jumbo_layer(x, m[f"layer_{i}"], m["jumbo_mlp"], heads, C, rope)
     x = _ln(x, m["norm"])
     x = _dense(x, params["decoder_proj"])
     enc_cls, img = x[:, :C], x[:, C:]
@@ -138,15 +166,19 @@ def mae_loss(params, images_u8, noise, *, layers, dim, heads, dec_layers, dec_di
 
 
 def classifier_logits(params, images_nhwc, *, layers, dim, heads, patch, posemb="learnable", C=3,
-                      bn_stats=None, training=True):
+                      bn_stats=None, training=True, rope_theta=100.0):
     m = params["model"]
     B, H, W, _ = images_nhwc.shape
     g = H // patch
     pos = fixed_sincos2d_embeddings(g, g, dim) if posemb == "sincos2d" else None
     x = patch_embed(images_nhwc, m["embed"], pos, patch, dim)
     x = torch.cat([m["cls_tokens"].expand(B, -1, -1), x], 1)
+    rope = None
+    if posemb == "rope":
+        cs = rope_cos_sin(torch.arange(g * g, device=x.device), g, dim // heads, rope_theta, x.dtype)
+        rope = (tuple(t[None] for t in cs), C)
     for i in range(layers):
-        x = jumbo_layer(x, m[f"layer_{i}"], m["jumbo_mlp"], heads, C)
+        x = jumbo_layer(x, m[f"layer_{i}"], m["jumbo_mlp"], heads, C, rope)
     x = _ln(x, m["norm"])
     x = x[:, :C].reshape(B, -1)
     head = m["head"]

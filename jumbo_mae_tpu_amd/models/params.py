@@ -413,6 +413,9 @@ class ParamStore:
                         break
                 if not ok:
                     if strict:
+                        if s.path[-2:] in (("embed", "wpe"), ("embed", "rope_theta")):
+                            from ..ckpt.checkpoint import POSEMB_MISMATCH
+                            raise KeyError(f"{s.key}: {POSEMB_MISMATCH}")
                         raise KeyError(s.key)
                     continue
                 arr = np.asarray(node, dtype=np.float32)

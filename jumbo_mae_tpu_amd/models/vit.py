@@ -31,6 +31,7 @@ from ..ops import blocks
 from ..ops import dropout as Dr
 from ..ops import functional as Fn
 from ..ops import mae as mae_ops
+from ..ops import rope as Rp
 from ..utils.posemb import fixed_sincos2d_embeddings
 from .params import ParamStore, const_, ones_, trunc_normal_, trunc_normal_t, zeros_
 
@@ -107,8 +108,10 @@ class Attention:
         self.wo_k = store.handle(_dense_kernel(store, path + ("wo", "kernel"), (heads, hd), (dim,), trainable))
         self.wo_b = store.handle(_bias(store, path + ("wo", "bias"), (dim,), trainable))
 
-    def __call__(self, x2d, B, S, rng=None, det=True, seeds=None):
+    def __call__(self, x2d, B, S, rng=None, det=True, seeds=None, rope=None):
         qkv = Fn.linear(x2d, self.qkv_k, self.qkv_b).view(B, S, 3 * self.dim)
+        if rope is not None:  # before the monitors: they see what the softmax sees
+            qkv = Fn.rope(qkv, self.heads, rope)
         if AS._COLLECTOR is not None:  # the attention monitor's probe pass (ops/attn_stats.py collecting)
             AS.observe(qkv, self.heads)
         if AM._COLLECTOR is not None:  # the attention maps' probe pass (ops/attn_maps.py collecting)
@@ -261,7 +264,7 @@ class JumboLayer:
     def dropout_rate(self):
         return self.cfg.dropout
 
-    def __call__(self, x, rng=None, det=True, link_in=None, link_out=None, masks=None, seeds=None):
+    def __call__(self, x, rng=None, det=True, link_in=None, link_out=None, masks=None, seeds=None, rope=None):
         B, S, D = x.shape
         C = self.C
         p = self.cfg.droppath
@@ -270,9 +273,9 @@ class JumboLayer:
             m1 = _mask(masks, 0, p, B, rng, x.device, det)
             m3 = _mask(masks, 1, p, B, rng, x.device, det)
             m2 = _mask(masks, 2, p, B, rng, x.device, det)
-            return blocks.jumbo_block(self, x, m1, m2, m3, link_in, link_out, _drops(sd, self.cfg.dropout, True))
+            return blocks.jumbo_block(self, x, m1, m2, m3, link_in, link_out, _drops(sd, self.cfg.dropout, True), rope)
         h = self.norm1(x)
-        a = self.attn(h, B, S, rng, det, sd and sd[0:2])
+        a = self.attn(h, B, S, rng, det, sd and sd[0:2], rope)
         x = Fn.residual(x, a, self.scale1, _mask(masks, 0, p, B, rng, x.device, det))
 
         # NB: the jumbo residual is added to the *normalized* CLS token (modeling.py:197-199),
@@ -314,16 +317,16 @@ class ViTLayer:
     def dropout_rate(self):
         return self.attn.dropout
 
-    def __call__(self, x, rng=None, det=True, link_in=None, link_out=None, masks=None, seeds=None):
+    def __call__(self, x, rng=None, det=True, link_in=None, link_out=None, masks=None, seeds=None, rope=None):
         B, S, D = x.shape
         p = self.droppath
         sd = seeds if seeds is not None else _layer_seeds(self.attn.dropout, rng, x.device, det, 4)
         if use_fused_blocks() and self.attn.dropout < 1.0:
             m1 = _mask(masks, 0, p, B, rng, x.device, det)
             m2 = _mask(masks, 1, p, B, rng, x.device, det)
-            return blocks.vit_block(self, x, m1, m2, link_in, link_out, _drops(sd, self.attn.dropout, False))
+            return blocks.vit_block(self, x, m1, m2, link_in, link_out, _drops(sd, self.attn.dropout, False), rope)
         h = self.norm1(x)
-        a = self.attn(h, B, S, rng, det, sd and sd[0:2])
+        a = self.attn(h, B, S, rng, det, sd and sd[0:2], rope)
         x = Fn.residual(x, a, self.scale1, _mask(masks, 0, p, B, rng, x.device, det))
         h = self.norm2(x)
         f = self.ff(h, rng, det, sd and sd[2:4])
@@ -339,6 +342,8 @@ class JumboViT:
         self.cfg = cfg
         D, p, g = cfg.dim, cfg.patch_size, cfg.grid
         P = prefix
+        if cfg.posemb == "rope":  # no position leaf and no table at the embedding: every attention layer rotates q, k
+            Rp.check_head_dim(cfg.head_dim)
         # embed/wte: HWIO (p,p,3,D) == GEMM kernel [(ph,pw,c), D], stored D x (p*p*3)
         self.wte_k = store.handle(_dense_kernel(store, P + ("embed", "wte", "kernel"), (p, p, 3), (D,), trainable))
         self.wte_b = store.handle(_bias(store, P + ("embed", "wte", "bias"), (D,), trainable))
@@ -364,10 +369,18 @@ class JumboViT:
             store.pad()
         self.norm = LayerNorm(store, P + ("norm",), D, trainable)
         store.pad()
+        if cfg.posemb == "rope":
+            # a frozen one-element leaf, never read by the forward (cfg.rope_theta is): it marks the tree, so that
+            # loading into or from a model with another --posemb / --rope-theta fails instead of passing silently
+            # (ckpt/checkpoint.py check_posemb; a sincos2d tree and a bare rope tree would hold the same leaves).
+            # Last and padded, so that every other segment keeps its aligned offset.
+            store.add(P + ("embed", "rope_theta"), (1,), const_(float(cfg.rope_theta)), trainable=False)
+            store.pad()
         self._posemb_cache = {}
 
     def posemb_table(self, device) -> torch.Tensor | None:
-        """Constant sincos table [g*g, D] (fp32), or None for learnable posemb."""
+        """Constant sincos table [g*g, D] (fp32), or None for learnable posemb and for rope (which
+        adds nothing at the embedding: ``embed_finish`` without a table writes the embeddings as they are)."""
         if self.cfg.posemb != "sincos2d":
             return None
         key = str(device)
@@ -398,8 +411,20 @@ class JumboViT:
             self._posemb_cache[key] = torch.arange(n, device=device)
         return self._posemb_cache[key]
 
-    def blocks(self, x: torch.Tensor, rng=None, det=True) -> torch.Tensor:
-        return _run_layers(self.layers, x, rng, det, self.cfg.grad_ckpt, in_dropout=self.cfg.dropout)
+    def rope(self, ids: torch.Tensor | None, device) -> "Rp.Rope | None":
+        """The attention layers' rotary descriptor of one forward (None unless ``posemb == "rope"``):
+        ``ids`` = the kept patches' indices ([K] shared or [B, K] per sample; the mask kernel's int32
+        copy is used as it is, so the tensor is static under graph capture), None = every patch in order."""
+        cfg = self.cfg
+        if cfg.posemb != "rope":
+            return None
+        table = Rp.rope_table(cfg.grid, cfg.head_dim, cfg.rope_theta, device)
+        return Rp.Rope(cfg.num_cls_tokens, cfg.grid, table, None if ids is None else mae_ops._i32(ids))
+
+    def blocks(self, x: torch.Tensor, rng=None, det=True, ids: torch.Tensor | None = None) -> torch.Tensor:
+        """``ids``: as for ``embed_rows`` (what the rotary embedding takes its coordinates from)."""
+        return _run_layers(self.layers, x, rng, det, self.cfg.grad_ckpt, in_dropout=self.cfg.dropout,
+                           rope=self.rope(ids, x.device))
 
 
 def cls_features(encoder: "JumboViT", rows: torch.Tensor, B: int, drop=None, det: bool = True) -> torch.Tensor:
@@ -414,15 +439,16 @@ def cls_features(encoder: "JumboViT", rows: torch.Tensor, B: int, drop=None, det
     return h.reshape(B, C * cfg.dim)
 
 
-def _run_layers(layers, x, rng, det, grad_ckpt, in_dropout=0.0):
+def _run_layers(layers, x, rng, det, grad_ckpt, in_dropout=0.0, rope=None):
     """The layer loop; consecutive fused blocks are chained by ``blocks.Link`` hand-offs (not
     under activation checkpointing, whose recompute would re-run forwards out of order).
-    ``in_dropout``: dropout of the stack's input (its seed drawn with the layers' seeds)."""
+    ``in_dropout``: dropout of the stack's input (its seed drawn with the layers' seeds).
+    ``rope``: the rotary descriptor every layer's attention gets (ops/rope.py), or None."""
     masks = droppath_masks(layers, x.shape[0], rng, x.device, det)
     x, seeds = dropout_seed_pool(layers, rng, x.device, det, head=(x, in_dropout))
     if grad_ckpt and torch.is_grad_enabled():
         for layer, m, sd in zip(layers, masks, seeds):
-            x = _checkpointed(layer, x, rng, det, m, sd)
+            x = _checkpointed(layer, x, rng, det, m, sd, rope)
         return x
     link = None
     for i, layer in enumerate(layers):
@@ -432,12 +458,12 @@ def _run_layers(layers, x, rng, det, grad_ckpt, in_dropout=0.0):
             # the upper block's LN1 rides on this block's last residual pass (forward hand-off)
             ln1 = (up.norm1.g, up.norm1.b) if up is not None and blocks.FWD_LINKS else None
             nxt = blocks.Link(ln1)
-        x = layer(x, rng, det, link_in=link, link_out=nxt, masks=masks[i], seeds=seeds[i])
+        x = layer(x, rng, det, link_in=link, link_out=nxt, masks=masks[i], seeds=seeds[i], rope=rope)
         link = nxt
     return x
 
 
-def _checkpointed(layer, x, rng, det, masks=None, seeds=None):
+def _checkpointed(layer, x, rng, det, masks=None, seeds=None, rope=None):
     """One layer under activation checkpointing (reference ``nn.remat``, modeling.py:232,280).
 
     The recompute in backward must see exactly the forward's random draws: droppath / dropout
@@ -454,13 +480,13 @@ def _checkpointed(layer, x, rng, det, masks=None, seeds=None):
     def run(inp):
         calls[0] += 1
         if calls[0] == 1:
-            return layer(inp, rng, det, masks=masks, seeds=seeds)
+            return layer(inp, rng, det, masks=masks, seeds=seeds, rope=rope)
         g = None
         if rng is not None:
             g = torch.Generator(device=rng.device)
             g.set_state(state)
         with store.uses_suppressed():
-            return layer(inp, g, det, masks=masks, seeds=seeds)
+            return layer(inp, g, det, masks=masks, seeds=seeds, rope=rope)
 
     return torch.utils.checkpoint.checkpoint(run, x, use_reentrant=False)
 

@@ -97,8 +97,13 @@ class Drops(NamedTuple):
     jo: torch.Tensor | None = None
 
 
-def _attn_fwd(attn, h1, B, S, dr: Drops | None = None):
+def _attn_fwd(attn, h1, B, S, dr: Drops | None = None, rope=None):
+    """``rope`` (an ``ops.rope.Rope``, or None): q and k of the patch rows are rotated in place right
+    after the QKV GEMM, so the monitors, the attention kernels and the saved qkv all hold what the
+    softmax sees."""
     qkv = P.linear_fwd(h1, attn.qkv_k, attn.qkv_b)
+    if rope is not None:
+        P.rope_(qkv.view(B, S, -1), attn.heads, rope.n_cls, rope.gw, rope.table, rope.pos)
     if AS._COLLECTOR is not None:  # the attention monitor's probe pass (ops/attn_stats.py collecting)
         AS.observe(qkv.view(B, S, -1), attn.heads)
     if AM._COLLECTOR is not None:  # the attention maps' probe pass (ops/attn_maps.py collecting)
@@ -113,10 +118,15 @@ def _od(dr: Drops | None, name: str, base):
     return None if dr is None else (getattr(dr, name), dr.rate, base)
 
 
-def _attn_bwd(attn, da, h1, qkv, o, lse, B, S, wo_bias_done=False, dr: Drops | None = None):
+def _attn_bwd(attn, da, h1, qkv, o, lse, B, S, wo_bias_done=False, dr: Drops | None = None, rope=None):
     do = P.linear_bwd(da, o.view(B * S, -1), attn.wo_k, attn.wo_b, bias_done=wo_bias_done)
-    dqkv, bd = P.attn_bwd(do, qkv.view(B, S, -1), o, lse, attn.heads, attn.qkv_b,
+    # with rope the attention backward's dqkv is the gradient of the ROTATED q and k: the QKV bias
+    # gradient is the column sum of the un-rotated one, so the kernels' fused bias gradient stays off
+    # (hbias None -> bias_done False) and linear_bwd sums the columns after the inverse rotation
+    dqkv, bd = P.attn_bwd(do, qkv.view(B, S, -1), o, lse, attn.heads, attn.qkv_b if rope is None else None,
                           drop=(dr.attn, dr.rate) if dr is not None else None)
+    if rope is not None:
+        dqkv = P.rope_(dqkv.view(B, S, -1), attn.heads, rope.n_cls, rope.gw, rope.table, rope.pos, inverse=True)
     return P.linear_bwd(dqkv.view(B * S, -1), h1, attn.qkv_k, attn.qkv_b, bias_done=bd)
 
 
@@ -157,13 +167,13 @@ def _ff_handles(ff):
 
 class JumboBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, layer, m1, m2, m3, link_in, link_out, train=True, dr=None):
+    def forward(ctx, x, anchor, layer, m1, m2, m3, link_in, link_out, train=True, dr=None, rope=None):
         B, S, D = x.shape
         C = layer.C
         J = C * D
         dt = layer.norm1.g.store.compute_dtype
         h1, mu1, rs1 = _ln1_fwd(x, layer, link_in, dt)
-        qkv, o, lse, a = _attn_fwd(layer.attn, h1, B, S, dr)
+        qkv, o, lse, a = _attn_fwd(layer.attn, h1, B, S, dr, rope)
         # residual + LN2 of the patch rows in one pass
         x1, hp, mup, rsp = P.residual_ln_fwd(x, a, layer.scale1, m1, layer.norm2.g, layer.norm2.b, C,
                                              drop=_od(dr, "wo", a))
@@ -192,6 +202,7 @@ class JumboBlockFn(torch.autograd.Function):
         ctx.gelu_deriv = (jd, fd)  # FF1 saved gelu'(h) instead of h (jumbo MLP, patch FF)
         ctx.gelu_rate = rate  # hidden dropout folded into uint8 gelu' codes (P.gd_decode)
         ctx.dr = dr
+        ctx.rope = rope
         if link_out is not None:
             link_out.spec = P.ResSpec(fy, layer.scale2, m2, layer.ff.w2.b, C, drop=_od(dr, "fo", fy))
         return x2
@@ -200,7 +211,7 @@ class JumboBlockFn(torch.autograd.Function):
     def backward(ctx, dx2):
         with P.paired_wgrads():  # FF2 + FF1 and Wo + QKV weight gradients as grouped launches
             dx = _jumbo_bwd(ctx, dx2)
-        return dx, None, None, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None, None, None
 
 
 def _jumbo_bwd(ctx, dx2):
@@ -242,7 +253,7 @@ def _jumbo_bwd(ctx, dx2):
                         res=P.ResSpec(a3[:, C:], layer.scale1, m1, layer.attn.wo_b, 0, da3[:, C:],
                                       drop=_od(dr, "wo", a)), h=hp)
     # ---- attention branch: dx = dx1 + LN1'(Attn'(s1 * dp1 * dx1))
-    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr)
+    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr, ctx.rope)
     return _ln1_bwd(ctx, dh1, x, mu1, rs1, layer, dx1, h1)
 
 
@@ -268,21 +279,21 @@ def _ln1_bwd(ctx, dh1, x, mu1, rs1, layer, dx1, h1=None):
 
 
 def jumbo_block(layer, x, m1=None, m2=None, m3=None, link_in: Link | None = None, link_out: Link | None = None,
-                dr: Drops | None = None):
+                dr: Drops | None = None, rope=None):
     _note_uses(layer.norm1.g, layer.norm1.b, layer.norm2.g, layer.norm2.b, layer.norm3.g, layer.norm3.b,
                layer.scale1, layer.scale2, layer.scale3, *_attn_handles(layer.attn), *_ff_handles(layer.ff),
                *_ff_handles(layer.jumbo_mlp))
     return JumboBlockFn.apply(x.contiguous(), layer.norm1.g.param, layer, m1, m2, m3, link_in, link_out,
-                              torch.is_grad_enabled(), dr)
+                              torch.is_grad_enabled(), dr, rope)
 
 
 class ViTBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, layer, m1, m2, link_in, link_out, train=True, dr=None):
+    def forward(ctx, x, anchor, layer, m1, m2, link_in, link_out, train=True, dr=None, rope=None):
         B, S, D = x.shape
         dt = layer.norm1.g.store.compute_dtype
         h1, mu1, rs1 = _ln1_fwd(x, layer, link_in, dt)
-        qkv, o, lse, a = _attn_fwd(layer.attn, h1, B, S, dr)
+        qkv, o, lse, a = _attn_fwd(layer.attn, h1, B, S, dr, rope)
         x1, h2, mu2, rs2 = P.residual_ln_fwd(x, a, layer.scale1, m1, layer.norm2.g, layer.norm2.b, 0,
                                              drop=_od(dr, "wo", a))
         fpre, fg, fy, fd = _ff_fwd(layer.ff, h2, train, dr.rate if dr is not None else 0.0, dr and dr.fh,
@@ -299,6 +310,7 @@ class ViTBlockFn(torch.autograd.Function):
         ctx.gelu_deriv = (False, fd)
         ctx.gelu_rate = dr.rate if dr is not None else 0.0
         ctx.dr = dr
+        ctx.rope = rope
         if link_out is not None:
             link_out.spec = P.ResSpec(fy, layer.scale2, m2, layer.ff.w2.b, 0, drop=_od(dr, "fo", fy))
         return x2
@@ -307,7 +319,7 @@ class ViTBlockFn(torch.autograd.Function):
     def backward(ctx, dx2):
         with P.paired_wgrads():  # FF2 + FF1 and Wo + QKV weight gradients as grouped launches
             dx = _vit_bwd(ctx, dx2)
-        return dx, None, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None, None
 
 
 def _vit_bwd(ctx, dx2):
@@ -326,13 +338,13 @@ def _vit_bwd(ctx, dx2):
     # LN2' with the attention-residual backward of its dx fused in (never write autograd's dx2)
     dx1, da, bd = P.ln_bwd(dh2, x1, mu2, rs2, layer.norm2.g, layer.norm2.b, dres=dx2,
                            res=P.ResSpec(a, layer.scale1, m1, layer.attn.wo_b, drop=_od(dr, "wo", a)), h=h2)
-    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr)
+    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr, ctx.rope)
     return _ln1_bwd(ctx, dh1, x, mu1, rs1, layer, dx1, h1)
 
 
 def vit_block(layer, x, m1=None, m2=None, link_in: Link | None = None, link_out: Link | None = None,
-              dr: Drops | None = None):
+              dr: Drops | None = None, rope=None):
     _note_uses(layer.norm1.g, layer.norm1.b, layer.norm2.g, layer.norm2.b, layer.scale1, layer.scale2,
                *_attn_handles(layer.attn), *_ff_handles(layer.ff))
     return ViTBlockFn.apply(x.contiguous(), layer.norm1.g.param, layer, m1, m2, link_in, link_out,
-                            torch.is_grad_enabled(), dr)
+                            torch.is_grad_enabled(), dr, rope)

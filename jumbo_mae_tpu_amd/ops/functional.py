@@ -162,6 +162,30 @@ def attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     return _Attention.apply(qkv, heads)
 
 
+# ------------------------------------------------------------------ rotary position embedding
+class _Rope(torch.autograd.Function):
+    """qkv [B, S, 3 * H * hd] -> a copy with q and k of the patch rows rotated (ops/rope.py); the
+    gradient is the transpose applied to a copy of the incoming one."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads: int, rope):
+        ctx.heads, ctx.rope = heads, rope
+        return P.rope_(qkv.clone(memory_format=torch.contiguous_format), heads, rope.n_cls, rope.gw, rope.table,
+                       rope.pos)
+
+    @staticmethod
+    def backward(ctx, dout):
+        r = ctx.rope
+        d = dout.clone(memory_format=torch.contiguous_format)
+        return P.rope_(d, ctx.heads, r.n_cls, r.gw, r.table, r.pos, inverse=True), None, None
+
+
+def rope(qkv: torch.Tensor, heads: int, rope) -> torch.Tensor:
+    """The per-op path's rotary embedding (``rope``: an ``ops.rope.Rope``); the fused blocks rotate
+    their own qkv in place (ops/blocks.py)."""
+    return _Rope.apply(qkv, heads, rope)
+
+
 # ---------------------------------------------------------------- classification loss + accuracy
 def cls_loss_torch(logits, labels_int, plan=None, smoothing: float = 0.0, criterion: str = "ce"):
     """The torch composition of models/classifier.py on integer labels: scattered one-hot ->

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from ..models.params import Handle
 from . import _ext
+from .rope import rope_torch
 
 LN_EPS = 1e-6
 _GELU_C = math.sqrt(2.0 / math.pi)
@@ -164,6 +165,7 @@ _FEAT_STATS_OURS = True  # representation monitor's Gram matrix and uniformity s
 _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc/optim.hip seg_stats), else the torch composition
 _ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused kernel (csrc/attn_stats.hip), else the torch composition
 _ATTN_MAPS_OURS = True  # attention maps' rollout step on the fused kernels (csrc/attn_rollout.hip), else the torch composition
+_ROPE_OURS = True  # rotary position embedding of q and k on the kernel (csrc/rope.hip), else the torch composition
 
 
 NARROW_MAX_M = 4096  # csrc/gemm_plan.h GEMM_NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles
@@ -740,6 +742,26 @@ def residual_bwd(dout3: torch.Tensor, y2: torch.Tensor | None, hs: Handle | None
     if mark_ready and _trainable(hs):
         hs.ready()
     return dy, done
+
+
+# ------------------------------------------------------------------------------ rotary position embedding
+def rope_(qkv: torch.Tensor, heads: int, n_cls: int, gw: int, table: torch.Tensor, pos: torch.Tensor | None = None,
+          inverse: bool = False) -> torch.Tensor:
+    """Rotates q and k of the patch rows ``t >= n_cls`` of qkv [B, S, 3 * heads * hd] IN PLACE and
+    returns it (ops/rope.py holds the definition; ``inverse``: the transpose, for the gradient).
+    The HIP kernel takes every head dim that is a multiple of 16 -- all that have attention
+    kernels -- and never touches v or the CLS rows; other multiples of 4, the CPU and
+    ``_ROPE_OURS = False`` take the torch composition ``rope_torch`` on the q|k patch rows."""
+    B, S, W = qkv.shape
+    hd = W // (3 * heads)
+    if _ROPE_OURS and hip(qkv) and hd % 16 == 0 and qkv.dtype in (torch.bfloat16, torch.float32):
+        if not qkv.is_contiguous():
+            raise ValueError("rope_: qkv must be contiguous")
+        return _ext.load().rope_apply(qkv, heads, n_cls, gw, table, pos, inverse)
+    with torch.no_grad():
+        out = rope_torch(qkv, heads, n_cls, gw, table, pos, inverse)
+        qkv.view(B, S, 3, heads, hd)[:, n_cls:, :2].copy_(out.view(B, S, 3, heads, hd)[:, n_cls:, :2])
+    return qkv
 
 
 # ------------------------------------------------------------------------------ attention

@@ -45,7 +45,11 @@ def _model(p: argparse.ArgumentParser, posemb: str):
     p.add_argument("--layerscale", action="store_true", default=False)
     p.add_argument("--patch-size", type=int, default=16)
     p.add_argument("--image-size", type=int, default=224)
-    p.add_argument("--posemb", default=posemb)
+    p.add_argument("--posemb", default=posemb,
+                   help="learnable | sincos2d | rope -- encoder position embedding: a learnable or fixed sincos2d "
+                        "table added at the patch embedding, or rope = axial 2-D rotary embedding of q and k in every "
+                        "attention layer (no table, nothing to resize at another --image-size)")
+    p.add_argument("--rope-theta", type=float, default=100.0, help="base of the rotary frequencies (--posemb rope)")
     p.add_argument("--pooling", default="cls")
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--droppath", type=float, default=0.1)

@@ -46,6 +46,7 @@ from .meter import AverageMeter, Logger
 def build_model(args, device, dtype) -> PretrainModel:
     vc = ViTConfig(layers=args.layers, dim=args.dim, heads=args.heads, labels=args.labels, layerscale=args.layerscale,
                    patch_size=args.patch_size, image_size=args.image_size, posemb=args.posemb, pooling=args.pooling,
+                   rope_theta=args.rope_theta,
                    dropout=args.dropout, droppath=args.droppath, grad_ckpt=args.grad_ckpt,
                    image_mask_ratio=args.image_mask_ratio, linear_probing=False)
     dc = DecoderConfig(dec_layers=args.dec_layers, dec_dim=args.dec_dim, dec_heads=args.dec_heads,
