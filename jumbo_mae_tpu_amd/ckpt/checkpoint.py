@@ -156,6 +156,43 @@ def check_posemb(src: dict, dst: dict) -> None:
         raise ValueError(f"checkpoint of {name(sk, st)} into a model of {name(dk, dt)}: {POSEMB_MISMATCH}")
 
 
+QKNORM_MISMATCH = ("the checkpoint and the model differ in QK-norm: pass the --qk-norm (and, for a pretrain model, the "
+                   "--dec-qk-norm) the checkpoint was trained with")
+
+
+def qknorm_leaves(tree: dict, path: tuple = ()) -> set:
+    """The paths of the QK-norm scales (``.../attn/q_norm/scale``, ``.../attn/k_norm/scale``) in a params tree."""
+    out = set()
+    for k, v in tree.items():
+        if isinstance(v, dict):
+            out |= qknorm_leaves(v, path + (k,))
+        elif k == "scale" and path[-1:] in (("q_norm",), ("k_norm",)):
+            out.add(path + (k,))
+    return out
+
+
+def check_qknorm(src: dict, dst: dict) -> None:
+    """Loading the tree ``src`` into a model whose fresh tree is ``dst`` (same root): both hold QK-norm scales
+    in the same attention layers, or neither does.  A model with QK-norm never takes a checkpoint without it
+    with scales left at ones -- the weights were trained against un-normalised logits -- and the other way round
+    the scales would be dropped silently."""
+    # (a finetune model holds no decoder: only the attention layers present on both sides are compared)
+    s = {p for p in qknorm_leaves(src) if _has_path(dst, p[:-2])}
+    d = {p for p in qknorm_leaves(dst) if _has_path(src, p[:-2])}
+    if s != d:
+        diff = sorted("/".join(p) for p in s ^ d)
+        side = "the checkpoint" if s - d else "the model"
+        raise ValueError(f"only {side} has the QK-norm scale {diff[0]} ({len(diff)} such leaves): {QKNORM_MISMATCH}")
+
+
+def _has_path(tree: dict, path: tuple) -> bool:
+    for k in path:
+        if not (isinstance(tree, dict) and k in tree):
+            return False
+        tree = tree[k]
+    return True
+
+
 def load_pretrained_params(url: str, params: dict, log=print) -> dict:
     """Merge the ``model`` subtree of a pretrained checkpoint into ``params`` (a Flax tree).
 
@@ -167,6 +204,7 @@ def load_pretrained_params(url: str, params: dict, log=print) -> dict:
     src = new.get("model", new)
     dst = params["model"]
     check_posemb(src, dst)
+    check_qknorm(src, dst)
     overlap = len(set(src).intersection(dst))
     log(f"[*] load pretrained params with overlap of {overlap}/{len(dst)}")
 

@@ -11,6 +11,8 @@ Here the standard ViT parts keep timm names (``patch_embed.proj``, ``blocks.i.at
   model/jumbo_mlp/w{1,2}              -> jumbo_mlp.fc{1,2}.{weight,bias}
   model/layer_i/norm3                 -> blocks.i.norm3.{weight,bias}
   model/layer_i/scale{1,2,3}          -> blocks.i.ls{1,2,3}.gamma
+  model/layer_i/attn/{q,k}_norm/scale -> blocks.i.attn.{q,k}_norm.weight (--qk-norm rms; timm ``qk_norm=True``
+                                         with an RMSNorm ``norm_layer``: weight only, no bias)
   model/head/Dense_0                  -> head.{weight,bias}
   model/head/BatchNorm_0              -> head_bn.{weight,bias}
 """
@@ -80,6 +82,9 @@ def flax_to_torch(params: dict, exclude_heads: bool = False, num_cls: int = 3, i
         sd[f"blocks.{i}.attn.qkv.bias"] = np.concatenate([_t(a[n]["bias"]).reshape(-1) for n in ("wq", "wk", "wv")])
         sd[f"blocks.{i}.attn.proj.weight"] = _t(a["wo"]["kernel"]).reshape(-1, D).T.copy()
         sd[f"blocks.{i}.attn.proj.bias"] = _t(a["wo"]["bias"])
+        for n in ("q_norm", "k_norm"):
+            if n in a:
+                sd[f"blocks.{i}.attn.{n}.weight"] = _t(a[n]["scale"])
         for j, n in ((1, "w1"), (2, "w2")):
             sd[f"blocks.{i}.mlp.fc{j}.weight"] = _t(layer["ff"][n]["kernel"]).T.copy()
             sd[f"blocks.{i}.mlp.fc{j}.bias"] = _t(layer["ff"][n]["bias"])
@@ -147,6 +152,12 @@ def torch_to_flax(sd: dict, num_heads: int, exclude_heads: bool = False, learnab
                        "bias": qkvb[j * D:(j + 1) * D].reshape(num_heads, hd).copy()}
         attn["wo"] = {"kernel": sd[p + "attn.proj.weight"].T.reshape(num_heads, hd, D).copy(),
                       "bias": sd[p + "attn.proj.bias"]}
+        for n in ("q_norm", "k_norm"):
+            if p + f"attn.{n}.weight" in sd:
+                if p + f"attn.{n}.bias" in sd:
+                    raise ValueError(f"{p}attn.{n}.bias: a LayerNorm QK-norm with a bias has no counterpart here "
+                                     "(--qk-norm rms is scale only)")
+                attn[n] = {"scale": sd[p + f"attn.{n}.weight"]}
         layer = {"attn": attn,
                  "ff": {f"w{j}": {"kernel": sd[p + f"mlp.fc{j}.weight"].T.copy(), "bias": sd[p + f"mlp.fc{j}.bias"]}
                         for j in (1, 2)}}

@@ -26,6 +26,7 @@ class ViTConfig:
     image_size: int = 224
     posemb: Literal["learnable", "sincos2d", "rope"] = "learnable"
     rope_theta: float = 100.0  # base of the axial rotary frequencies (posemb == "rope", ops/rope.py)
+    qk_norm: Literal["none", "rms"] = "none"  # RMSNorm of q and k per head before the softmax (ops/qknorm.py)
     pooling: Literal["cls", "gap"] = "cls"  # accepted for CLI parity, unused (modeling.py:272)
 
     dropout: float = 0.0
@@ -79,6 +80,7 @@ class DecoderConfig:
     dec_heads: int = 8
     dec_layerscale: bool = False
     dec_posemb: Literal["learnable", "sincos2d"] = "learnable"  # ignored by the reference (Q10)
+    dec_qk_norm: Literal["none", "rms"] = "none"  # QK-norm of the decoder's attention (no rope there)
     dec_dropout: float = 0.0
     dec_droppath: float = 0.0
     grad_ckpt: bool = False

@@ -1960,6 +1960,103 @@ torch::Tensor rope_apply(torch::Tensor qkv, int64_t heads, int64_t n_cls, int64_
   return qkv;
 }
 
+// ------------------------------------------------------------------------------ QK-norm
+// the rope arguments of qknorm_fwd / qknorm_bwd, checked as rope_apply checks them; table absent = no rotation
+struct QknRope {
+  const float* table = nullptr;
+  int G = 0;
+  const int* pos = nullptr;
+  long posB = 0;
+};
+
+QknRope qkn_rope(const char* fn, const torch::Tensor& qkv, int64_t hd, int64_t n_cls, int64_t gw,
+                 const c10::optional<torch::Tensor>& table, const c10::optional<torch::Tensor>& pos) {
+  QknRope r;
+  if (!(table.has_value() && table->defined())) {
+    TORCH_CHECK(!(pos.has_value() && pos->defined()), fn, ": pos without a table");
+    return r;
+  }
+  const auto& t = *table;
+  const int64_t B = qkv.size(0), S = qkv.size(1);
+  TORCH_CHECK(n_cls >= 0 && n_cls <= S && gw >= 1, fn, ": n_cls must be in 0..S and gw positive");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.dim() == 3 && t.size(0) >= 1 && t.size(1) == hd / 4 &&
+                  t.size(2) == 2 && t.is_contiguous() && t.device() == qkv.device(),
+              fn, ": table must be a contiguous fp32 [G, hd / 4, 2] tensor on qkv's device");
+  const int64_t G = t.size(0), Sp = S - n_cls;
+  TORCH_CHECK(G * gw < INT_MAX, fn, ": table too large");
+  if (pos.has_value() && pos->defined()) {
+    const auto& p = *pos;
+    TORCH_CHECK(p.scalar_type() == torch::kInt32 && p.is_contiguous() && p.device() == qkv.device() &&
+                    ((p.dim() == 1 && p.size(0) == Sp) || (p.dim() == 2 && p.size(0) == B && p.size(1) == Sp)),
+                fn, ": pos must be a contiguous int32 [S - n_cls] or [B, S - n_cls] tensor on qkv's device");
+    r.pos = p.data_ptr<int>();
+    r.posB = p.dim() == 2 ? (long)Sp : 0;
+  } else {
+    TORCH_CHECK(Sp <= G * gw, fn, ": the table covers fewer positions than the sequence has patch rows");
+  }
+  r.table = t.data_ptr<float>();
+  r.G = (int)G;
+  return r;
+}
+
+int64_t qkn_check(const char* fn, const torch::Tensor& qkv, int64_t heads, const torch::Tensor& g_q,
+                  const torch::Tensor& g_k) {
+  TORCH_CHECK(qkv.is_cuda(), fn, ": qkv must be a GPU tensor");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), fn, ": qkv must be a contiguous [B, S, 3 heads hd] tensor");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 || qkv.scalar_type() == torch::kFloat32, fn,
+              ": qkv must be bf16 or fp32");
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && W % (3 * heads) == 0, fn, ": the last dim must be 3 heads hd");
+  const int64_t hd = W / (3 * heads);
+  TORCH_CHECK(B * S < INT_MAX && W < INT_MAX, fn, ": qkv too large");
+  TORCH_CHECK(B == 0 || S == 0 || jm_qknorm_bwd_blocks((int)B, (int)S, (int)heads, (int)hd) > 0, fn,
+              ": hd must be one of 32, 64, 80, 96, 128");
+  for (const auto* g : {&g_q, &g_k})
+    TORCH_CHECK(g->scalar_type() == torch::kFloat32 && g->dim() == 1 && g->size(0) == hd && g->is_contiguous() &&
+                    g->device() == qkv.device() && reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
+                fn, ": g_q and g_k must be contiguous 16-byte aligned fp32 [hd] tensors on qkv's device");
+  return hd;
+}
+
+// normalises (and, with a table, rotates) q and k of qkv in place; returns saved [B, S, 2 heads hd], their input bits
+torch::Tensor qknorm_fwd(torch::Tensor qkv, int64_t heads, torch::Tensor g_q, torch::Tensor g_k, int64_t n_cls,
+                         int64_t gw, c10::optional<torch::Tensor> table, c10::optional<torch::Tensor> pos) {
+  const char* fn = "qknorm_fwd";
+  const int64_t hd = qkn_check(fn, qkv, heads, g_q, g_k);
+  const QknRope r = qkn_rope(fn, qkv, hd, n_cls, gw, table, pos);
+  const int64_t B = qkv.size(0), S = qkv.size(1);
+  auto saved = torch::empty({B, S, 2 * heads * hd}, qkv.options());
+  if (B == 0 || S == 0) return saved;
+  check_rc(jm_qknorm_fwd(qkv.data_ptr(), saved.data_ptr(), qkv.scalar_type() == torch::kBFloat16, (int)B, (int)S,
+                         (int)heads, (int)hd, g_q.data_ptr<float>(), g_k.data_ptr<float>(), (int)n_cls, (int)gw,
+                         r.table, r.G, r.pos, r.posB, stream()),
+           fn);
+  return saved;
+}
+
+// dx over the q and k thirds of dqkv in place; returns dg fp32 [2, hd] = (dg_q, dg_k)
+torch::Tensor qknorm_bwd(torch::Tensor dqkv, torch::Tensor saved, int64_t heads, torch::Tensor g_q, torch::Tensor g_k,
+                         int64_t n_cls, int64_t gw, c10::optional<torch::Tensor> table,
+                         c10::optional<torch::Tensor> pos) {
+  const char* fn = "qknorm_bwd";
+  const int64_t hd = qkn_check(fn, dqkv, heads, g_q, g_k);
+  const QknRope r = qkn_rope(fn, dqkv, hd, n_cls, gw, table, pos);
+  const int64_t B = dqkv.size(0), S = dqkv.size(1);
+  TORCH_CHECK(saved.scalar_type() == dqkv.scalar_type() && saved.is_contiguous() && saved.device() == dqkv.device() &&
+                  saved.numel() == B * S * 2 * heads * hd,
+              fn, ": saved must be a contiguous [B, S, 2 heads hd] tensor of dqkv's dtype and device");
+  auto fopt = dqkv.options().dtype(torch::kFloat32);
+  if (B == 0 || S == 0) return torch::zeros({2, hd}, fopt);
+  const int nb = jm_qknorm_bwd_blocks((int)B, (int)S, (int)heads, (int)hd);
+  auto part = torch::empty({nb, 2, hd}, fopt.dtype(torch::kFloat64));
+  auto dg = torch::empty({2, hd}, fopt);
+  check_rc(jm_qknorm_bwd(dqkv.data_ptr(), saved.data_ptr(), dqkv.scalar_type() == torch::kBFloat16, (int)B, (int)S,
+                         (int)heads, (int)hd, g_q.data_ptr<float>(), g_k.data_ptr<float>(), (int)n_cls, (int)gw,
+                         r.table, r.G, r.pos, r.posB, part.data_ptr<double>(), dg.data_ptr<float>(), stream()),
+           fn);
+  return dg;
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -1973,7 +2070,8 @@ py::dict debug_lines() {
       {"recon", jm_debug_line_recon},         {"knn", jm_debug_line_knn},
       {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout},
       {"distill", jm_debug_line_distill},     {"eval_report", jm_debug_line_eval_report},
-      {"feat_stats", jm_debug_line_feat_stats}, {"rope", jm_debug_line_rope}};
+      {"feat_stats", jm_debug_line_feat_stats}, {"rope", jm_debug_line_rope},
+      {"qknorm", jm_debug_line_qknorm}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -2134,6 +2232,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_apply", &rope_apply, py::arg("qkv"), py::arg("heads"), py::arg("n_cls"), py::arg("gw"), py::arg("table"),
         py::arg("pos") = py::none(), py::arg("inverse") = false,
         "axial 2-D rotary embedding of q and k of the patch rows of qkv [B, S, 3 heads hd], in place");
+  m.def("qknorm_fwd", &qknorm_fwd, py::arg("qkv"), py::arg("heads"), py::arg("g_q"), py::arg("g_k"),
+        py::arg("n_cls") = 0, py::arg("gw") = 1, py::arg("table") = py::none(), py::arg("pos") = py::none(),
+        "QK-norm: RMSNorm of q and k per head (then the rotary embedding, with a table) of qkv in place; returns the "
+        "saved pre-norm q|k");
+  m.def("qknorm_bwd", &qknorm_bwd, py::arg("dqkv"), py::arg("saved"), py::arg("heads"), py::arg("g_q"), py::arg("g_k"),
+        py::arg("n_cls") = 0, py::arg("gw") = 1, py::arg("table") = py::none(), py::arg("pos") = py::none(),
+        "QK-norm backward: dx over the q and k thirds of dqkv in place; returns fp32 [2, hd] = (dg_q, dg_k)");
+  m.def("qknorm_bwd_blocks", &jm_qknorm_bwd_blocks, py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("hd"),
+        "workgroups (rows of the partial workspace) of a qknorm_bwd launch");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

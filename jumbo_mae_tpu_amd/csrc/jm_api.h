@@ -475,3 +475,21 @@ int jm_debug_line_feat_stats();
 int jm_rope_apply(void* qkv, int bf16, int B, int S, int heads, int hd, int n_cls, int gw, const float* table, int G,
                   const int* pos, long posB, int inverse, hipStream_t st);
 int jm_debug_line_rope();
+
+// ---- qknorm.hip (QK-norm: per-head RMSNorm of q and k, rope fused behind it, ops/qknorm.py; -1 bad argument,
+// -2 failed launch; no atomics, no host sync, reruns bit-identical)
+// qkv / dqkv: contiguous bf16 or fp32 [B, S, 3, heads, hd], hd in {32, 64, 80, 96, 128}; saved: [B, S, 2, heads, hd]
+// of the same dtype; g_q, g_k: fp32 [hd], 16-byte aligned.  The v third is neither read nor written.  table / G /
+// pos / posB / gw / n_cls: as in jm_rope_apply; table null = no rotation (the other rope arguments are then ignored).
+// fwd: saved = the q|k bits of qkv; q|k of qkv = rotate(x r g), r = 1 / sqrt(mean(x^2) + 1e-6), rounded once
+int jm_qknorm_fwd(void* qkv, void* saved, int bf16, int B, int S, int heads, int hd, const float* g_q,
+                  const float* g_k, int n_cls, int gw, const float* table, int G, const int* pos, long posB,
+                  hipStream_t st);
+// bwd: the q|k thirds of dqkv (gradient of the normalised, rotated tensor) become the gradient of the pre-norm one,
+// r recomputed from saved, fp64 arithmetic; dg fp32 [2, hd] = (dg_q, dg_k) is WRITTEN from the per-workgroup partials
+// part fp64 [jm_qknorm_bwd_blocks(..), 2, hd] in workgroup order (a fixed tree; the grid depends on the shape only)
+int jm_qknorm_bwd(void* dqkv, const void* saved, int bf16, int B, int S, int heads, int hd, const float* g_q,
+                  const float* g_k, int n_cls, int gw, const float* table, int G, const int* pos, long posB,
+                  double* part, float* dg, hipStream_t st);
+int jm_qknorm_bwd_blocks(int B, int S, int heads, int hd);  // 0: unsupported shape
+int jm_debug_line_qknorm();

@@ -59,11 +59,18 @@ def _rotate(t, cs, C):
     return torch.cat([t[:, :C], rot], 1)
 
 
+def _rms(t, scale, eps=1e-6):
+    """q or k [B, S, H, hd] RMS-normalised over hd, times the layer's scale [hd]."""
+    return t / (t.pow(2).sum(-1, keepdim=True) / t.shape[-1] + eps).sqrt() * scale
+
+
 def _attention(x, p, heads, rope=None):
     """``rope`` = ((cos, sin), C): rotary embedding of q and k on the rows t >= C, or None."""
     q = _dense_general_in(x, p["wq"])
     k = _dense_general_in(x, p["wk"])
     v = _dense_general_in(x, p["wv"])
+    if "q_norm" in p:  # QK-norm (ops/qknorm.py): every row, CLS rows included, before the rotation
+        q, k = _rms(q, p["q_norm"]["scale"]), _rms(k, p["k_norm"]["scale"])
     if rope is not None:
         q, k = _rotate(q, *rope), _rotate(k, *rope)
     hd = q.shape[-1]

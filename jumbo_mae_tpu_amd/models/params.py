@@ -398,6 +398,14 @@ class ParamStore:
         """Copy leaves that exist in ``tree`` (and match shape). Returns (loaded, total)."""
         loaded = 0
         total = 0
+        if strict:  # QK-norm scales the model does not hold must not be dropped silently
+            from ..ckpt.checkpoint import QKNORM_MISMATCH, qknorm_leaves
+            extra = sorted("/".join(p) for p in qknorm_leaves(tree) if "/".join(p) not in self.by_key
+                           and "/".join(p[:-2] + ("wo", "bias")) in self.by_key  # (an attention layer of this model)
+                           and (not subtree or p[:len(subtree)] == subtree))
+            if extra:
+                raise KeyError(f"{extra[0]} (and {len(extra) - 1} more) in the checkpoint but not in the model: "
+                               f"{QKNORM_MISMATCH}")
         with torch.no_grad():
             for s in self.segments:
                 if subtree and s.path[:len(subtree)] != subtree:
@@ -416,6 +424,9 @@ class ParamStore:
                         if s.path[-2:] in (("embed", "wpe"), ("embed", "rope_theta")):
                             from ..ckpt.checkpoint import POSEMB_MISMATCH
                             raise KeyError(f"{s.key}: {POSEMB_MISMATCH}")
+                        if s.path[-2:] in (("q_norm", "scale"), ("k_norm", "scale")):
+                            from ..ckpt.checkpoint import QKNORM_MISMATCH
+                            raise KeyError(f"{s.key}: {QKNORM_MISMATCH}")
                         raise KeyError(s.key)
                     continue
                 arr = np.asarray(node, dtype=np.float32)

@@ -96,9 +96,11 @@ class FeedForward:
 
 
 class Attention:
-    """Multi-head self-attention; wq|wk|wv are adjacent segments read as one [3D, D] GEMM."""
+    """Multi-head self-attention; wq|wk|wv are adjacent segments read as one [3D, D] GEMM.
+    ``qk_norm == "rms"``: q and k are RMS-normalised per head before the softmax (ops/qknorm.py), with the
+    trainable scales ``q_norm/scale`` and ``k_norm/scale`` [hd], shared by the heads, initialised to ones."""
 
-    def __init__(self, store, path, dim, heads, dropout=0.0, trainable=True):
+    def __init__(self, store, path, dim, heads, dropout=0.0, trainable=True, qk_norm="none"):
         hd = dim // heads
         self.dim, self.heads, self.dropout = dim, heads, dropout
         ks = [_dense_kernel(store, path + (n, "kernel"), (dim,), (heads, hd), trainable) for n in ("wq", "wk", "wv")]
@@ -107,10 +109,18 @@ class Attention:
         self.qkv_b = store.handle(bs, (3 * dim,))
         self.wo_k = store.handle(_dense_kernel(store, path + ("wo", "kernel"), (heads, hd), (dim,), trainable))
         self.wo_b = store.handle(_bias(store, path + ("wo", "bias"), (dim,), trainable))
+        if qk_norm not in ("none", "rms"):
+            raise ValueError(f"qk_norm {qk_norm!r}: expected none or rms")
+        self.q_norm = self.k_norm = None
+        if qk_norm == "rms":  # not ``kernel`` leaves: no weight decay (Segment.is_kernel)
+            self.q_norm = store.handle(store.add(path + ("q_norm", "scale"), (hd,), ones_, trainable=trainable))
+            self.k_norm = store.handle(store.add(path + ("k_norm", "scale"), (hd,), ones_, trainable=trainable))
 
     def __call__(self, x2d, B, S, rng=None, det=True, seeds=None, rope=None):
         qkv = Fn.linear(x2d, self.qkv_k, self.qkv_b).view(B, S, 3 * self.dim)
-        if rope is not None:  # before the monitors: they see what the softmax sees
+        if self.q_norm is not None:  # norm, then the rotation, as one op
+            qkv = Fn.qknorm(qkv, self.q_norm, self.k_norm, self.heads, rope)
+        elif rope is not None:  # before the monitors: they see what the softmax sees
             qkv = Fn.rope(qkv, self.heads, rope)
         if AS._COLLECTOR is not None:  # the attention monitor's probe pass (ops/attn_stats.py collecting)
             AS.observe(qkv, self.heads)
@@ -241,7 +251,7 @@ class JumboLayer:
         D, J = cfg.dim, cfg.jumbo_dim
         self.cfg = cfg
         self.C = cfg.num_cls_tokens
-        self.attn = Attention(store, path + ("attn",), D, cfg.heads, cfg.dropout, trainable)
+        self.attn = Attention(store, path + ("attn",), D, cfg.heads, cfg.dropout, trainable, cfg.qk_norm)
         self.ff = FeedForward(store, path + ("ff",), D, cfg.hidden_dim, cfg.dropout, trainable)
         self.norm1 = LayerNorm(store, path + ("norm1",), D, trainable)
         self.norm2 = LayerNorm(store, path + ("norm2",), D, trainable)
@@ -295,8 +305,8 @@ class JumboLayer:
 class ViTLayer:
     """Standard pre-LN block used by the MAE decoder (modeling.py:150-167)."""
 
-    def __init__(self, store, path, dim, heads, layerscale, dropout, droppath, trainable=True):
-        self.attn = Attention(store, path + ("attn",), dim, heads, dropout, trainable)
+    def __init__(self, store, path, dim, heads, layerscale, dropout, droppath, trainable=True, qk_norm="none"):
+        self.attn = Attention(store, path + ("attn",), dim, heads, dropout, trainable, qk_norm)
         self.ff = FeedForward(store, path + ("ff",), dim, 4 * dim, dropout, trainable)
         self.norm1 = LayerNorm(store, path + ("norm1",), dim, trainable)
         self.norm2 = LayerNorm(store, path + ("norm2",), dim, trainable)
@@ -499,7 +509,8 @@ class MAEDecoder:
         self.layers = []
         for i in range(cfg.dec_layers):
             self.layers.append(ViTLayer(store, prefix + (f"dec_layer_{i}",), cfg.dec_dim, cfg.dec_heads,
-                                        cfg.dec_layerscale, cfg.dec_dropout, cfg.dec_droppath))
+                                        cfg.dec_layerscale, cfg.dec_dropout, cfg.dec_droppath,
+                                        qk_norm=cfg.dec_qk_norm))
             store.pad()
         self.dec_norm = LayerNorm(store, prefix + ("dec_norm",), cfg.dec_dim)
         store.pad()

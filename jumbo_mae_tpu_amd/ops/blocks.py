@@ -100,9 +100,14 @@ class Drops(NamedTuple):
 def _attn_fwd(attn, h1, B, S, dr: Drops | None = None, rope=None):
     """``rope`` (an ``ops.rope.Rope``, or None): q and k of the patch rows are rotated in place right
     after the QKV GEMM, so the monitors, the attention kernels and the saved qkv all hold what the
-    softmax sees."""
+    softmax sees.  A layer with QK-norm scales (``attn.q_norm`` / ``attn.k_norm``) normalises q and k
+    in that same pass -- one launch, the rotation fused behind the norm -- and returns the pre-norm
+    q|k the backward needs as ``qs`` (None without QK-norm)."""
     qkv = P.linear_fwd(h1, attn.qkv_k, attn.qkv_b)
-    if rope is not None:
+    qs = None
+    if attn.q_norm is not None:
+        qs = P.qknorm_fwd_(qkv.view(B, S, -1), attn.heads, attn.q_norm.master, attn.k_norm.master, rope)
+    elif rope is not None:
         P.rope_(qkv.view(B, S, -1), attn.heads, rope.n_cls, rope.gw, rope.table, rope.pos)
     if AS._COLLECTOR is not None:  # the attention monitor's probe pass (ops/attn_stats.py collecting)
         AS.observe(qkv.view(B, S, -1), attn.heads)
@@ -110,7 +115,7 @@ def _attn_fwd(attn, h1, B, S, dr: Drops | None = None, rope=None):
         AM.observe(qkv.view(B, S, -1), attn.heads)
     o, lse = P.attn_fwd(qkv.view(B, S, -1), attn.heads, drop=(dr.attn, dr.rate) if dr is not None else None)
     a = P.linear_fwd(o.view(B * S, -1), attn.wo_k, attn.wo_b)
-    return qkv, o, lse, a
+    return qkv, o, lse, a, qs
 
 
 def _od(dr: Drops | None, name: str, base):
@@ -118,14 +123,21 @@ def _od(dr: Drops | None, name: str, base):
     return None if dr is None else (getattr(dr, name), dr.rate, base)
 
 
-def _attn_bwd(attn, da, h1, qkv, o, lse, B, S, wo_bias_done=False, dr: Drops | None = None, rope=None):
+def _attn_bwd(attn, da, h1, qkv, o, lse, B, S, wo_bias_done=False, dr: Drops | None = None, rope=None, qs=None):
     do = P.linear_bwd(da, o.view(B * S, -1), attn.wo_k, attn.wo_b, bias_done=wo_bias_done)
     # with rope the attention backward's dqkv is the gradient of the ROTATED q and k: the QKV bias
     # gradient is the column sum of the un-rotated one, so the kernels' fused bias gradient stays off
-    # (hbias None -> bias_done False) and linear_bwd sums the columns after the inverse rotation
-    dqkv, bd = P.attn_bwd(do, qkv.view(B, S, -1), o, lse, attn.heads, attn.qkv_b if rope is None else None,
+    # (hbias None -> bias_done False) and linear_bwd sums the columns after the inverse rotation.
+    # The same holds for QK-norm (``qs``: the forward's pre-norm q|k): dqkv is the gradient of the
+    # normalised q and k, and the bias takes the column sum of what qknorm_bwd_ leaves in its place
+    plain = rope is None and qs is None
+    dqkv, bd = P.attn_bwd(do, qkv.view(B, S, -1), o, lse, attn.heads, attn.qkv_b if plain else None,
                           drop=(dr.attn, dr.rate) if dr is not None else None)
-    if rope is not None:
+    if qs is not None:  # un-rotate + norm backward in one launch; dg is final for this use of the scales
+        dqkv, dg = P.qknorm_bwd_(dqkv.view(B, S, -1), qs, attn.heads, attn.q_norm.master, attn.k_norm.master, rope)
+        attn.q_norm.accumulate_grad(dg[0])
+        attn.k_norm.accumulate_grad(dg[1])
+    elif rope is not None:
         dqkv = P.rope_(dqkv.view(B, S, -1), attn.heads, rope.n_cls, rope.gw, rope.table, rope.pos, inverse=True)
     return P.linear_bwd(dqkv.view(B * S, -1), h1, attn.qkv_k, attn.qkv_b, bias_done=bd)
 
@@ -158,7 +170,7 @@ def _note_uses(*handles):
 
 
 def _attn_handles(attn):
-    return (attn.qkv_k, attn.qkv_b, attn.wo_k, attn.wo_b)
+    return (attn.qkv_k, attn.qkv_b, attn.wo_k, attn.wo_b, attn.q_norm, attn.k_norm)  # (the last two may be None)
 
 
 def _ff_handles(ff):
@@ -173,7 +185,7 @@ class JumboBlockFn(torch.autograd.Function):
         J = C * D
         dt = layer.norm1.g.store.compute_dtype
         h1, mu1, rs1 = _ln1_fwd(x, layer, link_in, dt)
-        qkv, o, lse, a = _attn_fwd(layer.attn, h1, B, S, dr, rope)
+        qkv, o, lse, a, qs = _attn_fwd(layer.attn, h1, B, S, dr, rope)
         # residual + LN2 of the patch rows in one pass
         x1, hp, mup, rsp = P.residual_ln_fwd(x, a, layer.scale1, m1, layer.norm2.g, layer.norm2.b, C,
                                              drop=_od(dr, "wo", a))
@@ -196,7 +208,7 @@ class JumboBlockFn(torch.autograd.Function):
         else:
             P.residual_fwd(pin, fy, layer.scale2, m2, out=x2[:, C:], drop=_od(dr, "fo", fy))
         ctx.save_for_backward(x, mu1, rs1, h1, qkv, o, lse, a, x1, muc, rsc, hcb, jpre, jg, jy,
-                              hp, mup, rsp, fpre, fg, fy, m1, m2, m3)
+                              hp, mup, rsp, fpre, fg, fy, m1, m2, m3, qs)
         ctx.layer = layer
         ctx.link_in, ctx.link_out = link_in, link_out
         ctx.gelu_deriv = (jd, fd)  # FF1 saved gelu'(h) instead of h (jumbo MLP, patch FF)
@@ -216,7 +228,7 @@ class JumboBlockFn(torch.autograd.Function):
 
 def _jumbo_bwd(ctx, dx2):
     (x, mu1, rs1, h1, qkv, o, lse, a, x1, muc, rsc, hcb, jpre, jg, jy,
-     hp, mup, rsp, fpre, fg, fy, m1, m2, m3) = ctx.saved_tensors
+     hp, mup, rsp, fpre, fg, fy, m1, m2, m3, qs) = ctx.saved_tensors
     layer = ctx.layer
     dr = ctx.dr
     B, S, D = x.shape
@@ -253,7 +265,7 @@ def _jumbo_bwd(ctx, dx2):
                         res=P.ResSpec(a3[:, C:], layer.scale1, m1, layer.attn.wo_b, 0, da3[:, C:],
                                       drop=_od(dr, "wo", a)), h=hp)
     # ---- attention branch: dx = dx1 + LN1'(Attn'(s1 * dp1 * dx1))
-    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr, ctx.rope)
+    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr, ctx.rope, qs)
     return _ln1_bwd(ctx, dh1, x, mu1, rs1, layer, dx1, h1)
 
 
@@ -293,7 +305,7 @@ class ViTBlockFn(torch.autograd.Function):
         B, S, D = x.shape
         dt = layer.norm1.g.store.compute_dtype
         h1, mu1, rs1 = _ln1_fwd(x, layer, link_in, dt)
-        qkv, o, lse, a = _attn_fwd(layer.attn, h1, B, S, dr, rope)
+        qkv, o, lse, a, qs = _attn_fwd(layer.attn, h1, B, S, dr, rope)
         x1, h2, mu2, rs2 = P.residual_ln_fwd(x, a, layer.scale1, m1, layer.norm2.g, layer.norm2.b, 0,
                                              drop=_od(dr, "wo", a))
         fpre, fg, fy, fd = _ff_fwd(layer.ff, h2, train, dr.rate if dr is not None else 0.0, dr and dr.fh,
@@ -304,7 +316,7 @@ class ViTBlockFn(torch.autograd.Function):
             link_out.put_h1(x2, h1n, mun, rsn)
         else:
             x2 = P.residual_fwd(x1, fy, layer.scale2, m2, drop=_od(dr, "fo", fy))
-        ctx.save_for_backward(x, mu1, rs1, h1, qkv, o, lse, a, x1, mu2, rs2, h2, fpre, fg, fy, m1, m2)
+        ctx.save_for_backward(x, mu1, rs1, h1, qkv, o, lse, a, x1, mu2, rs2, h2, fpre, fg, fy, m1, m2, qs)
         ctx.layer = layer
         ctx.link_in, ctx.link_out = link_in, link_out
         ctx.gelu_deriv = (False, fd)
@@ -323,7 +335,7 @@ class ViTBlockFn(torch.autograd.Function):
 
 
 def _vit_bwd(ctx, dx2):
-    x, mu1, rs1, h1, qkv, o, lse, a, x1, mu2, rs2, h2, fpre, fg, fy, m1, m2 = ctx.saved_tensors
+    x, mu1, rs1, h1, qkv, o, lse, a, x1, mu2, rs2, h2, fpre, fg, fy, m1, m2, qs = ctx.saved_tensors
     layer = ctx.layer
     dr = ctx.dr
     B, S, D = x.shape
@@ -338,7 +350,7 @@ def _vit_bwd(ctx, dx2):
     # LN2' with the attention-residual backward of its dx fused in (never write autograd's dx2)
     dx1, da, bd = P.ln_bwd(dh2, x1, mu2, rs2, layer.norm2.g, layer.norm2.b, dres=dx2,
                            res=P.ResSpec(a, layer.scale1, m1, layer.attn.wo_b, drop=_od(dr, "wo", a)), h=h2)
-    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr, ctx.rope)
+    dh1 = _attn_bwd(layer.attn, da, h1, qkv, o, lse, B, S, bd, dr, ctx.rope, qs)
     return _ln1_bwd(ctx, dh1, x, mu1, rs1, layer, dx1, h1)
 
 

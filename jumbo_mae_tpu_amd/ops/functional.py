@@ -186,6 +186,37 @@ def rope(qkv: torch.Tensor, heads: int, rope) -> torch.Tensor:
     return _Rope.apply(qkv, heads, rope)
 
 
+# ------------------------------------------------------------------------------------ QK-norm
+class _QKNorm(torch.autograd.Function):
+    """qkv [B, S, 3 * H * hd] -> a copy with q and k normalised per head (and rotated, with
+    ``rope``); saves the pre-norm q|k, from which the backward recomputes r (ops/qknorm.py)."""
+
+    @staticmethod
+    def forward(ctx, qkv, qp, kp, hq: Handle, hk: Handle, heads: int, rope):
+        out = qkv.clone(memory_format=torch.contiguous_format)
+        saved = P.qknorm_fwd_(out, heads, hq.master, hk.master, rope)
+        ctx.save_for_backward(saved)
+        ctx.hq, ctx.hk, ctx.heads, ctx.rope = hq, hk, heads, rope
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (saved,) = ctx.saved_tensors
+        d = dout.clone(memory_format=torch.contiguous_format)
+        d, dg = P.qknorm_bwd_(d, saved, ctx.heads, ctx.hq.master, ctx.hk.master, ctx.rope)
+        ctx.hq.accumulate_grad(dg[0])
+        ctx.hk.accumulate_grad(dg[1])
+        return d, None, None, None, None, None, None
+
+
+def qknorm(qkv: torch.Tensor, hq: Handle, hk: Handle, heads: int, rope=None) -> torch.Tensor:
+    """The per-op path's QK-norm (``hq`` / ``hk``: the layer's q_norm / k_norm scale handles;
+    ``rope``: an ``ops.rope.Rope`` or None); the fused blocks normalise their own qkv in place."""
+    hq.note_use()
+    hk.note_use()
+    return _QKNorm.apply(qkv, hq.param, hk.param, hq, hk, heads, rope)
+
+
 # ---------------------------------------------------------------- classification loss + accuracy
 def cls_loss_torch(logits, labels_int, plan=None, smoothing: float = 0.0, criterion: str = "ce"):
     """The torch composition of models/classifier.py on integer labels: scattered one-hot ->

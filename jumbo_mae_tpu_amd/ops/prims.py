@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from ..models.params import Handle
 from . import _ext
+from . import qknorm as QN
 from .rope import rope_torch
 
 LN_EPS = 1e-6
@@ -166,6 +167,7 @@ _NORMS_OURS = True  # norm monitor's per-leaf statistics on the fused pass (csrc
 _ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused kernel (csrc/attn_stats.hip), else the torch composition
 _ATTN_MAPS_OURS = True  # attention maps' rollout step on the fused kernels (csrc/attn_rollout.hip), else the torch composition
 _ROPE_OURS = True  # rotary position embedding of q and k on the kernel (csrc/rope.hip), else the torch composition
+_QKNORM_OURS = True  # QK-norm (+ rope) of q and k on the fused kernels (csrc/qknorm.hip), else the torch composition
 
 
 NARROW_MAX_M = 4096  # csrc/gemm_plan.h GEMM_NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles
@@ -762,6 +764,63 @@ def rope_(qkv: torch.Tensor, heads: int, n_cls: int, gw: int, table: torch.Tenso
         out = rope_torch(qkv, heads, n_cls, gw, table, pos, inverse)
         qkv.view(B, S, 3, heads, hd)[:, n_cls:, :2].copy_(out.view(B, S, 3, heads, hd)[:, n_cls:, :2])
     return qkv
+
+
+# ------------------------------------------------------------------------------ QK-norm
+def _qknorm_hip(qkv: torch.Tensor, heads: int) -> bool:
+    """The routing rule of ``rope_``: HIP tensors in bf16 / fp32 at a head dim that has attention
+    kernels take csrc/qknorm.hip; the CPU, other dtypes and head dims and ``_QKNORM_OURS = False``
+    take the torch composition (ops/qknorm.py)."""
+    hd = qkv.shape[-1] // (3 * heads)
+    if _QKNORM_OURS and hip(qkv) and hd in QN.HEAD_DIMS and qkv.dtype in (torch.bfloat16, torch.float32):
+        if not qkv.is_contiguous():
+            raise ValueError("qknorm: qkv must be contiguous")
+        return True
+    return False
+
+
+def _qkn_scale(g: torch.Tensor) -> torch.Tensor:
+    """The kernel reads the fp32 master scale in 16-byte vectors: a view at an odd offset is copied."""
+    g = g.detach()
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.data_ptr() % 16:
+        g = g.float().clone(memory_format=torch.contiguous_format)
+    return g
+
+
+def _qkn_rope(rope):
+    return (0, 1, None, None) if rope is None else (rope.n_cls, rope.gw, rope.table, rope.pos)
+
+
+def qknorm_fwd_(qkv: torch.Tensor, heads: int, g_q: torch.Tensor, g_k: torch.Tensor, rope=None) -> torch.Tensor:
+    """QK-norm of q and k of qkv [B, S, 3 * heads * hd] IN PLACE (ops/qknorm.py holds the definition;
+    ``g_q`` / ``g_k``: the fp32 master scales [hd]; ``rope``: an ``ops.rope.Rope`` whose rotation is
+    fused behind the norm, or None) -- one launch.  Returns ``saved`` [B, S, 2 * heads * hd], the exact
+    pre-norm q|k bits the backward recomputes r from."""
+    B, S, W = qkv.shape
+    hd = W // (3 * heads)
+    if _qknorm_hip(qkv, heads):
+        return _ext.load().qknorm_fwd(qkv, heads, _qkn_scale(g_q), _qkn_scale(g_k), *_qkn_rope(rope))
+    with torch.no_grad():
+        v5 = qkv.view(B, S, 3, heads, hd)
+        saved = v5[:, :, :2].reshape(B, S, 2 * heads * hd).clone(memory_format=torch.contiguous_format)  # (the reshape alone is a view)
+        out = QN.qknorm_torch(qkv, heads, g_q.detach(), g_k.detach(), rope)
+        v5[:, :, :2].copy_(out.view(B, S, 3, heads, hd)[:, :, :2])
+    return saved
+
+
+def qknorm_bwd_(dqkv: torch.Tensor, saved: torch.Tensor, heads: int, g_q: torch.Tensor, g_k: torch.Tensor, rope=None):
+    """The backward of ``qknorm_fwd_``: the q and k thirds of ``dqkv`` (the gradient of what the
+    attention kernels consumed) become the gradient of the pre-norm q|k IN PLACE, v untouched.
+    Returns (dqkv, dg [2, hd] fp32 = (dg_q, dg_k)); the kernel's dg is a deterministic two-stage sum."""
+    B, S, W = dqkv.shape
+    hd = W // (3 * heads)
+    if _qknorm_hip(dqkv, heads):
+        dg = _ext.load().qknorm_bwd(dqkv, saved, heads, _qkn_scale(g_q), _qkn_scale(g_k), *_qkn_rope(rope))
+        return dqkv, dg
+    with torch.no_grad():
+        dx, dg = QN.qknorm_bwd_torch(dqkv, saved, heads, g_q.detach(), g_k.detach(), rope)
+        dqkv.view(B, S, 3, heads, hd)[:, :, :2].copy_(dx)
+    return dqkv, dg
 
 
 # ------------------------------------------------------------------------------ attention

@@ -50,6 +50,11 @@ def _model(p: argparse.ArgumentParser, posemb: str):
                         "table added at the patch embedding, or rope = axial 2-D rotary embedding of q and k in every "
                         "attention layer (no table, nothing to resize at another --image-size)")
     p.add_argument("--rope-theta", type=float, default=100.0, help="base of the rotary frequencies (--posemb rope)")
+    p.add_argument("--qk-norm", choices=("none", "rms"), default="none",
+                   help="rms = the encoder's attention RMS-normalises q and k per head before the softmax, with one "
+                        "trainable scale each per layer (the remedy for growing attention logits, val/attn_max_logit); "
+                        "fused with --posemb rope into one pass.  A checkpoint loads only into a model of the same "
+                        "--qk-norm")
     p.add_argument("--pooling", default="cls")
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--droppath", type=float, default=0.1)
@@ -161,6 +166,8 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--dec-heads", type=int, default=8)
     p.add_argument("--dec-layerscale", action="store_true", default=False)
     p.add_argument("--dec-posemb", default="sincos2d")
+    p.add_argument("--dec-qk-norm", choices=("none", "rms"), default="none",
+                   help="--qk-norm for the MAE decoder's attention layers")
     p.add_argument("--dec-dropout", type=float, default=0.0)
     p.add_argument("--dec-droppath", type=float, default=0.1)
     p.add_argument("--norm-pix-loss", action="store_true", default=False)
