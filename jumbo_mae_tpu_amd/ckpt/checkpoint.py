@@ -185,6 +185,39 @@ def check_qknorm(src: dict, dst: dict) -> None:
         raise ValueError(f"only {side} has the QK-norm scale {diff[0]} ({len(diff)} such leaves): {QKNORM_MISMATCH}")
 
 
+FFN_MISMATCH = ("the checkpoint and the model differ in the feed-forward kind: pass the --ffn (and, for a pretrain "
+                "model, the --dec-ffn; for a distillation teacher, the --teacher-ffn) the checkpoint was trained with")
+
+
+def ffn_nodes(tree: dict, path: tuple = ()) -> dict:
+    """{path of a feed-forward node: it is gated} of a params tree: the nodes ``.../ff`` and ``.../jumbo_mlp``
+    (they hold ``w1`` and ``w2``); gated = the node has the SwiGLU up projection ``w3``."""
+    out = {}
+    for k, v in tree.items():
+        if isinstance(v, dict):
+            if k in ("ff", "jumbo_mlp") and "w1" in v and "w2" in v:
+                out[path + (k,)] = "w3" in v
+            else:
+                out.update(ffn_nodes(v, path + (k,)))
+    return out
+
+
+def check_ffn(src: dict, dst: dict) -> None:
+    """Loading the tree ``src`` into a model whose fresh tree is ``dst`` (same root): every feed-forward present
+    on both sides is of the same kind.  Checked before any leaf is compared, so that a GELU checkpoint in a
+    SwiGLU model (or the reverse) fails naming the flag and the ``w3`` leaves, not with the shape mismatch of
+    ``w1/kernel`` (4 dim against the gated width)."""
+    s, d = ffn_nodes(src), ffn_nodes(dst)
+    missing = sorted("/".join(p + ("w3",)) for p in d if d[p] and p in s and not s[p])
+    extra = sorted("/".join(p + ("w3",)) for p in s if s[p] and p in d and not d[p])
+    if missing:
+        raise ValueError(f"the model (swiglu) holds {missing[0]} ({len(missing)} such feed-forwards) and the checkpoint "
+                         f"(gelu) does not: {FFN_MISMATCH}")
+    if extra:
+        raise ValueError(f"the checkpoint (swiglu) holds {extra[0]} ({len(extra)} such feed-forwards) and the model "
+                         f"(gelu) does not: {FFN_MISMATCH}")
+
+
 def _has_path(tree: dict, path: tuple) -> bool:
     for k in path:
         if not (isinstance(tree, dict) and k in tree):
@@ -205,6 +238,7 @@ def load_pretrained_params(url: str, params: dict, log=print) -> dict:
     dst = params["model"]
     check_posemb(src, dst)
     check_qknorm(src, dst)
+    check_ffn(src, dst)
     overlap = len(set(src).intersection(dst))
     log(f"[*] load pretrained params with overlap of {overlap}/{len(dst)}")
 

@@ -13,6 +13,8 @@ Here the standard ViT parts keep timm names (``patch_embed.proj``, ``blocks.i.at
   model/layer_i/scale{1,2,3}          -> blocks.i.ls{1,2,3}.gamma
   model/layer_i/attn/{q,k}_norm/scale -> blocks.i.attn.{q,k}_norm.weight (--qk-norm rms; timm ``qk_norm=True``
                                          with an RMSNorm ``norm_layer``: weight only, no bias)
+  model/layer_i/ff/{w1,w3,w2}         -> blocks.i.mlp.{fc1_g,fc1_x,fc2}.{weight,bias} (--ffn swiglu; timm ``SwiGLU``:
+                                         fc1_g the gate, fc1_x the up projection); the jumbo MLP alike
   model/head/Dense_0                  -> head.{weight,bias}
   model/head/BatchNorm_0              -> head_bn.{weight,bias}
 """
@@ -28,6 +30,22 @@ from ..utils.posemb import _sincos2d_np
 
 def _t(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+# Flax leaf -> timm module of a feed-forward: the GELU kind's (w1, w2), the gated kind's (w1, w3, w2)
+_FF_GELU = (("w1", "fc1"), ("w2", "fc2"))
+_FF_SWIGLU = (("w1", "fc1_g"), ("w3", "fc1_x"), ("w2", "fc2"))
+
+
+def _ff_to_torch(sd: dict, prefix: str, ff: dict) -> None:
+    for n, t in (_FF_SWIGLU if "w3" in ff else _FF_GELU):
+        sd[f"{prefix}{t}.weight"] = _t(ff[n]["kernel"]).T.copy()
+        sd[f"{prefix}{t}.bias"] = _t(ff[n]["bias"])
+
+
+def _ff_to_flax(sd: dict, prefix: str) -> dict:
+    names = _FF_SWIGLU if prefix + "fc1_g.weight" in sd else _FF_GELU
+    return {n: {"kernel": sd[f"{prefix}{t}.weight"].T.copy(), "bias": sd[f"{prefix}{t}.bias"]} for n, t in names}
 
 
 def flax_to_torch(params: dict, exclude_heads: bool = False, num_cls: int = 3, image_size: int = 224) -> dict:
@@ -60,9 +78,7 @@ def flax_to_torch(params: dict, exclude_heads: bool = False, num_cls: int = 3, i
         sd["norm.weight"] = _t(m["norm"]["scale"])
         sd["norm.bias"] = _t(m["norm"]["bias"])
     if "jumbo_mlp" in m:
-        for i, n in ((1, "w1"), (2, "w2")):
-            sd[f"jumbo_mlp.fc{i}.weight"] = _t(m["jumbo_mlp"][n]["kernel"]).T.copy()
-            sd[f"jumbo_mlp.fc{i}.bias"] = _t(m["jumbo_mlp"][n]["bias"])
+        _ff_to_torch(sd, "jumbo_mlp.", m["jumbo_mlp"])
     if "head" in m and not exclude_heads:
         h = m["head"]
         dense = h["Dense_0"] if "Dense_0" in h else h
@@ -85,9 +101,7 @@ def flax_to_torch(params: dict, exclude_heads: bool = False, num_cls: int = 3, i
         for n in ("q_norm", "k_norm"):
             if n in a:
                 sd[f"blocks.{i}.attn.{n}.weight"] = _t(a[n]["scale"])
-        for j, n in ((1, "w1"), (2, "w2")):
-            sd[f"blocks.{i}.mlp.fc{j}.weight"] = _t(layer["ff"][n]["kernel"]).T.copy()
-            sd[f"blocks.{i}.mlp.fc{j}.bias"] = _t(layer["ff"][n]["bias"])
+        _ff_to_torch(sd, f"blocks.{i}.mlp.", layer["ff"])
         for nn_ in ("norm1", "norm2", "norm3"):
             if nn_ in layer:
                 sd[f"blocks.{i}.{nn_}.weight"] = _t(layer[nn_]["scale"])
@@ -133,9 +147,8 @@ def torch_to_flax(sd: dict, num_heads: int, exclude_heads: bool = False, learnab
     m["cls_tokens"] = cls
     if "norm.weight" in sd:
         m["norm"] = {"scale": sd["norm.weight"], "bias": sd["norm.bias"]}
-    if "jumbo_mlp.fc1.weight" in sd:
-        m["jumbo_mlp"] = {f"w{j}": {"kernel": sd[f"jumbo_mlp.fc{j}.weight"].T.copy(),
-                                    "bias": sd[f"jumbo_mlp.fc{j}.bias"]} for j in (1, 2)}
+    if "jumbo_mlp.fc1.weight" in sd or "jumbo_mlp.fc1_g.weight" in sd:
+        m["jumbo_mlp"] = _ff_to_flax(sd, "jumbo_mlp.")
     if "head.weight" in sd and not exclude_heads:
         head = {"Dense_0": {"kernel": sd["head.weight"].T.copy(), "bias": sd["head.bias"]}}
         if "head_bn.weight" in sd:
@@ -158,9 +171,7 @@ def torch_to_flax(sd: dict, num_heads: int, exclude_heads: bool = False, learnab
                     raise ValueError(f"{p}attn.{n}.bias: a LayerNorm QK-norm with a bias has no counterpart here "
                                      "(--qk-norm rms is scale only)")
                 attn[n] = {"scale": sd[p + f"attn.{n}.weight"]}
-        layer = {"attn": attn,
-                 "ff": {f"w{j}": {"kernel": sd[p + f"mlp.fc{j}.weight"].T.copy(), "bias": sd[p + f"mlp.fc{j}.bias"]}
-                        for j in (1, 2)}}
+        layer = {"attn": attn, "ff": _ff_to_flax(sd, p + "mlp.")}
         for nn_ in ("norm1", "norm2", "norm3"):
             if p + nn_ + ".weight" in sd:
                 layer[nn_] = {"scale": sd[p + nn_ + ".weight"], "bias": sd[p + nn_ + ".bias"]}

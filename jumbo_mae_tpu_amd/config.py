@@ -2,7 +2,7 @@
 
 Parity: ``ViTBase`` / ``MAEDecoderBase`` of the reference
 (/root/reference/src/modeling.py:35-104).  Derived quantities (``head_dim``,
-``hidden_dim = 4*dim``, ``num_patches``) follow the reference exactly; the
+``hidden_dim = 4*dim`` for the GELU feed-forward, ``num_patches``) follow the reference exactly; the
 decoder record exposes the same fields with the ``dec_`` prefix.
 """
 
@@ -10,6 +10,17 @@ from __future__ import annotations
 
 from dataclasses import asdict, dataclass, field
 from typing import Literal
+
+def ffn_hidden(dim: int, ffn: str = "gelu") -> int:
+    """Hidden width of a feed-forward over ``dim`` channels: 4 dim for gelu; for swiglu the parameter-matched
+    width ceil((8 dim / 3) / 128) * 128 (three matrices instead of two; a multiple of 128 keeps every K on the
+    128-deep GEMM loop): 768 -> 2048, 1024 -> 2816, 1280 -> 3456, the jumbo MLP's 2304 -> 6144."""
+    if ffn == "gelu":
+        return 4 * dim
+    if ffn == "swiglu":
+        return -(-(8 * dim) // (3 * 128)) * 128
+    raise ValueError(f"ffn {ffn!r}: expected gelu or swiglu")
+
 
 NUM_CLS_TOKENS = 3  # jumbo: three CLS tokens concatenated into one 3*dim token (modeling.py:170,222)
 
@@ -27,6 +38,7 @@ class ViTConfig:
     posemb: Literal["learnable", "sincos2d", "rope"] = "learnable"
     rope_theta: float = 100.0  # base of the axial rotary frequencies (posemb == "rope", ops/rope.py)
     qk_norm: Literal["none", "rms"] = "none"  # RMSNorm of q and k per head before the softmax (ops/qknorm.py)
+    ffn: Literal["gelu", "swiglu"] = "gelu"  # feed-forward kind, the shared jumbo MLP's too (ops/swiglu.py)
     pooling: Literal["cls", "gap"] = "cls"  # accepted for CLI parity, unused (modeling.py:272)
 
     dropout: float = 0.0
@@ -44,11 +56,15 @@ class ViTConfig:
 
     @property
     def hidden_dim(self) -> int:
-        return 4 * self.dim
+        return ffn_hidden(self.dim, self.ffn)
 
     @property
     def jumbo_dim(self) -> int:
         return self.dim * self.num_cls_tokens
+
+    @property
+    def jumbo_hidden_dim(self) -> int:
+        return ffn_hidden(self.jumbo_dim, self.ffn)
 
     @property
     def grid(self) -> int:
@@ -81,6 +97,7 @@ class DecoderConfig:
     dec_layerscale: bool = False
     dec_posemb: Literal["learnable", "sincos2d"] = "learnable"  # ignored by the reference (Q10)
     dec_qk_norm: Literal["none", "rms"] = "none"  # QK-norm of the decoder's attention (no rope there)
+    dec_ffn: Literal["gelu", "swiglu"] = "gelu"  # feed-forward kind of the decoder blocks
     dec_dropout: float = 0.0
     dec_droppath: float = 0.0
     grad_ckpt: bool = False
@@ -93,7 +110,7 @@ class DecoderConfig:
 
     @property
     def hidden_dim(self) -> int:
-        return 4 * self.dec_dim
+        return ffn_hidden(self.dec_dim, self.dec_ffn)
 
     @property
     def grid(self) -> int:

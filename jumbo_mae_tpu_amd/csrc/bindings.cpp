@@ -2057,6 +2057,72 @@ torch::Tensor qknorm_bwd(torch::Tensor dqkv, torch::Tensor saved, int64_t heads,
   return dg;
 }
 
+// ------------------------------------------------------------------------------ SwiGLU gate (csrc/swiglu.hip)
+// Both return (status, result): a negative status (jm_api.h) is a shape the kernels do not take -- the result is then
+// an empty tensor and the caller (ops/prims.py) takes the torch composition.  rate <= 0: no dropout, seed ignored.
+struct SwDrop {
+  const int64_t* seed = nullptr;
+  uint32_t thr = 0;
+  float scale = 1.f;
+};
+
+static SwDrop sw_drop(const char* fn, const torch::Tensor& pre, const c10::optional<torch::Tensor>& seed, double rate) {
+  SwDrop d;
+  if (rate <= 0.0) return d;
+  TORCH_CHECK(seed.has_value() && seed->defined(), fn, ": a dropout rate needs a seed");
+  check_seed(*seed, pre);
+  const auto kp = keep_params(rate);
+  d.seed = seed->data_ptr<int64_t>();
+  d.thr = kp.first;
+  d.scale = kp.second;
+  return d;
+}
+
+static void sw_check(const char* fn, const torch::Tensor& pre) {
+  CHECK_CUDA(pre);
+  TORCH_CHECK(pre.scalar_type() == torch::kBFloat16 && pre.dim() == 2 && pre.is_contiguous() && pre.size(1) % 2 == 0,
+              fn, ": pre must be a contiguous bf16 [M, 2 Hs] tensor");
+  TORCH_CHECK(pre.size(0) < INT_MAX && pre.size(1) < INT_MAX, fn, ": pre too large");
+}
+
+std::tuple<int64_t, torch::Tensor> swiglu_fwd(torch::Tensor pre, c10::optional<torch::Tensor> seed, double rate) {
+  const char* fn = "swiglu_fwd";
+  sw_check(fn, pre);
+  const SwDrop d = sw_drop(fn, pre, seed, rate);
+  const int64_t M = pre.size(0), Hs = pre.size(1) / 2;
+  if (M == 0) return {-1, torch::empty({0}, pre.options())};
+  auto a = torch::empty({M, Hs}, pre.options());
+  const int rc = jm_swiglu_fwd(bf(pre), bfm(a), (int)M, (int)Hs, d.seed, d.thr, d.scale, stream());
+  if (rc < 0) return {rc, torch::empty({0}, pre.options())};
+  return {0, a};
+}
+
+std::tuple<int64_t, torch::Tensor> swiglu_bwd(torch::Tensor pre, torch::Tensor da, c10::optional<torch::Tensor> bias_grad,
+                                              c10::optional<torch::Tensor> seed, double rate) {
+  const char* fn = "swiglu_bwd";
+  sw_check(fn, pre);
+  const SwDrop d = sw_drop(fn, pre, seed, rate);
+  const int64_t M = pre.size(0), Hs = pre.size(1) / 2;
+  TORCH_CHECK(da.scalar_type() == torch::kBFloat16 && da.is_contiguous() && da.device() == pre.device() &&
+                  da.dim() == 2 && da.size(0) == M && da.size(1) == Hs,
+              fn, ": da must be a contiguous bf16 [M, Hs] tensor on pre's device");
+  float* bg = nullptr;
+  if (bias_grad.has_value() && bias_grad->defined()) {
+    TORCH_CHECK(bias_grad->scalar_type() == torch::kFloat32 && bias_grad->is_contiguous() &&
+                    bias_grad->numel() == 2 * Hs && bias_grad->device() == pre.device(),
+                fn, ": bias_grad must be a contiguous fp32 [2 Hs] tensor on pre's device");
+    bg = bias_grad->data_ptr<float>();
+  }
+  if (M == 0) return {-1, torch::empty({0}, pre.options())};
+  auto dpre = torch::empty_like(pre);
+  torch::Tensor ws;
+  if (bg) ws = torch::empty({jm_swiglu_ws_floats((int)M, (int)Hs)}, pre.options().dtype(torch::kFloat32));
+  const int rc = jm_swiglu_bwd(bf(pre), bf(da), bfm(dpre), bg, (int)M, (int)Hs, d.seed, d.thr, d.scale, stream(),
+                               bg ? ws.data_ptr<float>() : nullptr);
+  if (rc < 0) return {rc, torch::empty({0}, pre.options())};
+  return {0, dpre};
+}
+
 py::dict debug_lines() {
   py::dict d;
   const std::pair<const char*, int (*)()> tus[] = {
@@ -2071,7 +2137,7 @@ py::dict debug_lines() {
       {"attn_stats", jm_debug_line_attn_stats}, {"attn_rollout", jm_debug_line_attn_rollout},
       {"distill", jm_debug_line_distill},     {"eval_report", jm_debug_line_eval_report},
       {"feat_stats", jm_debug_line_feat_stats}, {"rope", jm_debug_line_rope},
-      {"qknorm", jm_debug_line_qknorm}};
+      {"qknorm", jm_debug_line_qknorm},       {"swiglu", jm_debug_line_swiglu}};
   for (const auto& t : tus) {
     const int line = t.second();
     if (line) d[t.first] = line;
@@ -2241,6 +2307,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "QK-norm backward: dx over the q and k thirds of dqkv in place; returns fp32 [2, hd] = (dg_q, dg_k)");
   m.def("qknorm_bwd_blocks", &jm_qknorm_bwd_blocks, py::arg("B"), py::arg("S"), py::arg("heads"), py::arg("hd"),
         "workgroups (rows of the partial workspace) of a qknorm_bwd launch");
+  m.def("swiglu_fwd", &swiglu_fwd, py::arg("pre"), py::arg("seed") = py::none(), py::arg("rate") = 0.0,
+        "SwiGLU gate: (status, a [M, Hs]) of pre [M, 2 Hs] = [gate | up]; a negative status: shape not taken");
+  m.def("swiglu_bwd", &swiglu_bwd, py::arg("pre"), py::arg("da"), py::arg("bias_grad") = py::none(),
+        py::arg("seed") = py::none(), py::arg("rate") = 0.0,
+        "SwiGLU gate backward: (status, dpre [M, 2 Hs]); bias_grad fp32 [2 Hs] += colsum(dpre)");
+  m.def("swiglu_ws_floats", &jm_swiglu_ws_floats, py::arg("M"), py::arg("Hs"),
+        "floats of a swiglu_bwd launch's partial-row workspace (0: shape not taken)");
   m.def("debug_lines", &debug_lines);
   m.def("debug_selftest", &debug_selftest);
 #ifdef JM_DEBUG

@@ -41,7 +41,7 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
 KERNELS = ["layernorm.hip", "elementwise.hip", "attention.hip", "optim.hip", "mae.hip", "gemm.hip", "gemm_tn.hip", "dropout.hip",
            "augment.hip", "augment_chain.hip", "loss.hip", "batchnorm.hip", "recon.hip", "knn.hip", "attn_stats.hip",
-           "attn_rollout.hip", "distill.hip", "eval_report.hip", "feat_stats.hip", "rope.hip", "qknorm.hip"]
+           "attn_rollout.hip", "distill.hip", "eval_report.hip", "feat_stats.hip", "rope.hip", "qknorm.hip", "swiglu.hip"]
 
 
 def _torch_paths():

@@ -493,3 +493,18 @@ int jm_qknorm_bwd(void* dqkv, const void* saved, int bf16, int B, int S, int hea
                   double* part, float* dg, hipStream_t st);
 int jm_qknorm_bwd_blocks(int B, int S, int heads, int hd);  // 0: unsupported shape
 int jm_debug_line_qknorm();
+
+// ---- swiglu.hip (the gate of the gated feed-forward, ops/swiglu.py; bf16; pre: contiguous [M, 2 Hs] = [gate | up],
+// a / da: contiguous [M, Hs], every pointer 16-byte aligned, Hs % 8 == 0; seed null = no hidden dropout, else the
+// keep bits of common.h drop_keep(seed, m Hs + c, thr), kept values times scale; -1 bad argument (Hs % 8, M <= 0, a
+// null or unaligned pointer), -2 an operand of 4 GiB or more, -3 failed launch; no atomics, reruns bit-identical)
+// a[m, c] = bf16(silu(pre[m, c]) pre[m, Hs + c] drop), fp32 arithmetic, one rounding
+int jm_swiglu_fwd(const uint16_t* pre, uint16_t* a, int M, int Hs, const int64_t* seed, uint32_t thr, float scale,
+                  hipStream_t st);
+// dpre[m, c] = bf16(da drop u sigma (1 + g (1 - sigma))), dpre[m, Hs + c] = bf16(da drop silu(g)); bias_grad (fp32
+// [2 Hs], may be null) += the column sums of the rounded dpre, through the partial rows ws (jm_swiglu_ws_floats
+// floats; may be null with bias_grad null)
+int jm_swiglu_bwd(const uint16_t* pre, const uint16_t* da, uint16_t* dpre, float* bias_grad, int M, int Hs,
+                  const int64_t* seed, uint32_t thr, float scale, hipStream_t st, float* ws);
+long jm_swiglu_ws_floats(int M, int Hs);  // 0: unsupported shape
+int jm_debug_line_swiglu();

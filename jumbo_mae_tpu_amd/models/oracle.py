@@ -80,6 +80,8 @@ def _attention(x, p, heads, rope=None):
 
 
 def _ff(x, p):
+    if "w3" in p:  # the gated feed-forward (ops/swiglu.py): w1 the gate, w3 the up projection
+        return _dense(F.silu(_dense(x, p["w1"])) * _dense(x, p["w3"]), p["w2"])
     return _dense(F.gelu(_dense(x, p["w1"]), approximate="tanh"), p["w2"])
 
 

@@ -406,6 +406,17 @@ class ParamStore:
             if extra:
                 raise KeyError(f"{extra[0]} (and {len(extra) - 1} more) in the checkpoint but not in the model: "
                                f"{QKNORM_MISMATCH}")
+            # a feed-forward of the other kind (--ffn): named before w1/kernel fails as a shape mismatch
+            from ..ckpt.checkpoint import check_ffn
+            own: dict = {}
+            for s in self.segments:
+                if subtree and s.path[:len(subtree)] != subtree:
+                    continue
+                node = own
+                for k in s.path[:-1]:
+                    node = node.setdefault(k, {})
+                node[s.path[-1]] = None
+            check_ffn(tree, own)
         with torch.no_grad():
             for s in self.segments:
                 if subtree and s.path[:len(subtree)] != subtree:

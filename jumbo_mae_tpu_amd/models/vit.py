@@ -24,7 +24,7 @@ import os
 import numpy as np
 import torch
 
-from ..config import DecoderConfig, ViTConfig
+from ..config import DecoderConfig, ViTConfig, ffn_hidden
 from ..ops import attn_maps as AM
 from ..ops import attn_stats as AS
 from ..ops import blocks
@@ -80,17 +80,57 @@ class LayerNorm:
         return Fn.layer_norm(x, self.g, self.b, out_dtype, row0)
 
 
-class FeedForward:
-    """Dense(4*dim) -> gelu(tanh) -> dropout -> Dense(dim) -> dropout (modeling.py:141-148)."""
+class _DenseView:
+    """A Dense over adjacent segments read through one handle pair (w1 | w3 of the gated feed-forward)."""
 
-    def __init__(self, store, path, dim, hidden, dropout=0.0, trainable=True):
-        self.w1 = Dense(store, path + ("w1",), dim, hidden, trainable)
+    def __init__(self, k, b):
+        self.k, self.b = k, b
+
+    def __call__(self, x):
+        return Fn.linear(x, self.k, self.b)
+
+
+FFN_KINDS = ("gelu", "swiglu")
+
+
+class FeedForward:
+    """``kind == "gelu"``: Dense(4*dim) -> gelu(tanh) -> dropout -> Dense(dim) -> dropout (modeling.py:141-148).
+    ``kind == "swiglu"``: W2 . dropout(silu(W1 x + b1) * (W3 x + b3)) + b2 -> dropout (ops/swiglu.py) with the
+    leaves w1 (gate), w3 (up) and w2; w1 | w3 are adjacent segments read as one [2 hidden, dim] GEMM (``w13``), the
+    way wq | wk | wv are."""
+
+    def __init__(self, store, path, dim, hidden, dropout=0.0, trainable=True, kind="gelu"):
+        if kind not in FFN_KINDS:
+            raise ValueError(f"ffn {kind!r}: expected gelu or swiglu")
+        self.kind = kind
+        if kind == "swiglu":
+            ks = [_dense_kernel(store, path + (n, "kernel"), (dim,), (hidden,), trainable) for n in ("w1", "w3")]
+            bs = [_bias(store, path + (n, "bias"), (hidden,), trainable) for n in ("w1", "w3")]
+            self.w13 = _DenseView(store.handle(ks, (2 * hidden, dim)), store.handle(bs, (2 * hidden,)))
+        else:
+            self.w1 = Dense(store, path + ("w1",), dim, hidden, trainable)
         self.w2 = Dense(store, path + ("w2",), hidden, dim, trainable)
         self.dropout = dropout
 
+    @property
+    def ff1(self):
+        """The FF1 Dense: w1, or w1 | w3 of the gated kind."""
+        return self.w13 if self.kind == "swiglu" else self.w1
+
     def __call__(self, x, rng=None, det=True, seeds=None):
-        h = self.w1(x, gelu=True)
-        h = _dropout(h, self.dropout, rng, det, seeds and seeds[0])
+        if self.kind == "swiglu":
+            pre = self.w13(x)
+            rate = self.dropout
+            if rate <= 0.0 or det:
+                h = Fn.swiglu(pre)
+            elif rate >= 1.0:
+                h = Fn.swiglu(pre) * 0.0
+            else:  # the mask indexes the gate's output, as the GELU kind's hidden dropout indexes gelu(h)
+                seed = seeds[0] if seeds else Dr.draw_seed(rng, pre.device)
+                h = Fn.swiglu(pre, (seed, rate))
+        else:
+            h = self.w1(x, gelu=True)
+            h = _dropout(h, self.dropout, rng, det, seeds and seeds[0])
         y = self.w2(h)
         return _dropout(y, self.dropout, rng, det, seeds and seeds[1])
 
@@ -252,7 +292,7 @@ class JumboLayer:
         self.cfg = cfg
         self.C = cfg.num_cls_tokens
         self.attn = Attention(store, path + ("attn",), D, cfg.heads, cfg.dropout, trainable, cfg.qk_norm)
-        self.ff = FeedForward(store, path + ("ff",), D, cfg.hidden_dim, cfg.dropout, trainable)
+        self.ff = FeedForward(store, path + ("ff",), D, cfg.hidden_dim, cfg.dropout, trainable, cfg.ffn)
         self.norm1 = LayerNorm(store, path + ("norm1",), D, trainable)
         self.norm2 = LayerNorm(store, path + ("norm2",), D, trainable)
         self.norm3 = LayerNorm(store, path + ("norm3",), J, trainable)
@@ -305,9 +345,10 @@ class JumboLayer:
 class ViTLayer:
     """Standard pre-LN block used by the MAE decoder (modeling.py:150-167)."""
 
-    def __init__(self, store, path, dim, heads, layerscale, dropout, droppath, trainable=True, qk_norm="none"):
+    def __init__(self, store, path, dim, heads, layerscale, dropout, droppath, trainable=True, qk_norm="none",
+                 ffn="gelu"):
         self.attn = Attention(store, path + ("attn",), dim, heads, dropout, trainable, qk_norm)
-        self.ff = FeedForward(store, path + ("ff",), dim, 4 * dim, dropout, trainable)
+        self.ff = FeedForward(store, path + ("ff",), dim, ffn_hidden(dim, ffn), dropout, trainable, ffn)
         self.norm1 = LayerNorm(store, path + ("norm1",), dim, trainable)
         self.norm2 = LayerNorm(store, path + ("norm2",), dim, trainable)
         self.droppath = droppath
@@ -366,11 +407,12 @@ class JumboViT:
                                               trainable=trainable))
         self.cls_tokens = store.handle(store.add(P + ("cls_tokens",), (1, cfg.num_cls_tokens, D), zeros_,
                                                  trainable=trainable))
-        self.jumbo_mlp = FeedForward(store, P + ("jumbo_mlp",), cfg.jumbo_dim, 4 * cfg.jumbo_dim,
-                                     cfg.dropout, trainable)
+        # (the same kind as the patch feed-forward)
+        self.jumbo_mlp = FeedForward(store, P + ("jumbo_mlp",), cfg.jumbo_dim, cfg.jumbo_hidden_dim,
+                                     cfg.dropout, trainable, cfg.ffn)
         # shared by every layer: its weight gradients are batched into one GEMM over all layers'
         # rows at the end of backward (ops/prims.py linear_bwd / flush_deferred_wgrads)
-        self.jumbo_mlp.w1.k.defer_wgrad = True
+        self.jumbo_mlp.ff1.k.defer_wgrad = True
         self.jumbo_mlp.w2.k.defer_wgrad = True
         store.pad()
         self.layers = []
@@ -510,7 +552,7 @@ class MAEDecoder:
         for i in range(cfg.dec_layers):
             self.layers.append(ViTLayer(store, prefix + (f"dec_layer_{i}",), cfg.dec_dim, cfg.dec_heads,
                                         cfg.dec_layerscale, cfg.dec_dropout, cfg.dec_droppath,
-                                        qk_norm=cfg.dec_qk_norm))
+                                        qk_norm=cfg.dec_qk_norm, ffn=cfg.dec_ffn))
             store.pad()
         self.dec_norm = LayerNorm(store, prefix + ("dec_norm",), cfg.dec_dim)
         store.pad()

@@ -146,7 +146,15 @@ def _ff_fwd(ff, h, train=True, rate=0.0, sh=None, so=None):
     """(saved, gelu, y, deriv): ``saved`` is gelu'(pre) when ``deriv`` (fused MFMA forward), else pre.
     With the dropout seed ``sh`` the hidden gelu(h) and gelu'(h) are masked together (in the GEMM
     epilogue, or one pass after; saved is then always the masked gelu').  The output's dropout is
-    applied by the residual kernels that read y (``_od``)."""
+    applied by the residual kernels that read y (``_od``).
+    A gated feed-forward (``ff.kind == "swiglu"``): saved = pre = [gate | up] of the one FF1 GEMM over w1 | w3,
+    the second slot holds the gate's output a (FF2's input), deriv is False; the hidden dropout is applied
+    inside the gate kernel and regenerated from the seed in the backward."""
+    if ff.kind == "swiglu":
+        pre = P.linear_fwd(h, ff.w13.k, ff.w13.b)
+        a = P.swiglu_fwd(pre, (sh, rate) if sh is not None else None)
+        y = P.linear_fwd(a, ff.w2.k, ff.w2.b)
+        return pre, a, y, False
     pre, g, deriv, dropped = P.linear_gelu_fwd_saved(h, ff.w1.k, ff.w1.b, need_pre=train,
                                                      drop=(sh, rate) if sh is not None else None)
     if sh is not None and not dropped:  # (the fused gelu' forward drops inside its epilogue)
@@ -156,8 +164,14 @@ def _ff_fwd(ff, h, train=True, rate=0.0, sh=None, so=None):
     return pre, g, y, deriv
 
 
-def _ff_bwd(ff, dy, h, pre, g, w2_bias_done=False, dx_add=None, deriv=False, rate=0.0):
-    """``rate``: the hidden dropout rate the forward folded into uint8 gelu' codes (``pre``)."""
+def _ff_bwd(ff, dy, h, pre, g, w2_bias_done=False, dx_add=None, deriv=False, rate=0.0, sh=None):
+    """``rate``: the hidden dropout rate the forward folded into uint8 gelu' codes (``pre``).  ``sh``: the hidden
+    dropout's seed, which the gated feed-forward's gate backward regenerates its mask from."""
+    if ff.kind == "swiglu":
+        da = P.linear_bwd(dy, g, ff.w2.k, ff.w2.b, bias_done=w2_bias_done)
+        hb13 = ff.w13.b if ff.w13.k.segs[0].trainable else None
+        dpre, bias_done = P.swiglu_bwd(pre, da, hb13, (sh, rate) if sh is not None else None)
+        return P.linear_bwd(dpre, h, ff.w13.k, ff.w13.b, bias_done=bias_done, dx_add=dx_add)
     hb1 = ff.w1.b if ff.w1.k.segs[0].trainable else None
     dpre, bias_done = P.linear_gelu_bwd(dy, g, pre, ff.w2.k, ff.w2.b, hb1, w2_bias_done, deriv, rate)
     return P.linear_bwd(dpre, h, ff.w1.k, ff.w1.b, bias_done=bias_done, dx_add=dx_add)
@@ -174,6 +188,8 @@ def _attn_handles(attn):
 
 
 def _ff_handles(ff):
+    if ff.kind == "swiglu":
+        return (ff.w13.k, ff.w13.b, ff.w2.k, ff.w2.b)
     return (ff.w1.k, ff.w1.b, ff.w2.k, ff.w2.b)
 
 
@@ -245,7 +261,7 @@ def _jumbo_bwd(ctx, dx2):
     djy, bd = P.residual_bwd(dcls, jy, layer.scale3, m3, dt, layer.jumbo_mlp.w2.b, drop=_od(dr, "jo", jy))
     # d hc = dcls + JumboMLP'(...) in fp32, the add fused into the jumbo dgrad's split-K reduce
     dhc = _ff_bwd(layer.jumbo_mlp, djy, hcb, jpre, jg, bd, dx_add=dcls.reshape(B, J),
-                  deriv=ctx.gelu_deriv[0], rate=ctx.gelu_rate)
+                  deriv=ctx.gelu_deriv[0], rate=ctx.gelu_rate, sh=dr and dr.jh)
     P.ln_bwd(dhc, x1[:, :C].reshape(B, 1, J), muc, rsc, layer.norm3.g, layer.norm3.b,
              out=dx1[:, :C].reshape(B, 1, J))
     # attention-residual backward of the CLS rows (the patch rows ride on LN2' below, which
@@ -258,7 +274,7 @@ def _jumbo_bwd(ctx, dx2):
         dfy, bd = fused
     else:
         dfy, bd = P.residual_bwd(dx2[:, C:], fy, layer.scale2, m2, dt, layer.ff.w2.b, drop=_od(dr, "fo", fy))
-    dhp = _ff_bwd(layer.ff, dfy, hp, fpre, fg, bd, deriv=ctx.gelu_deriv[1], rate=ctx.gelu_rate)
+    dhp = _ff_bwd(layer.ff, dfy, hp, fpre, fg, bd, deriv=ctx.gelu_deriv[1], rate=ctx.gelu_rate, sh=dr and dr.fh)
     # ... and the attention-residual backward of those rows in the same pass
     _, _, bd = P.ln_bwd(dhp, x1[:, C:], mup, rsp, layer.norm2.g, layer.norm2.b, dres=dx2[:, C:],
                         out=dx1[:, C:],
@@ -346,7 +362,7 @@ def _vit_bwd(ctx, dx2):
         dfy, bd = fused
     else:
         dfy, bd = P.residual_bwd(dx2, fy, layer.scale2, m2, dt, layer.ff.w2.b, drop=_od(dr, "fo", fy))
-    dh2 = _ff_bwd(layer.ff, dfy, h2, fpre, fg, bd, deriv=ctx.gelu_deriv[1], rate=ctx.gelu_rate)
+    dh2 = _ff_bwd(layer.ff, dfy, h2, fpre, fg, bd, deriv=ctx.gelu_deriv[1], rate=ctx.gelu_rate, sh=dr and dr.fh)
     # LN2' with the attention-residual backward of its dx fused in (never write autograd's dx2)
     dx1, da, bd = P.ln_bwd(dh2, x1, mu2, rs2, layer.norm2.g, layer.norm2.b, dres=dx2,
                            res=P.ResSpec(a, layer.scale1, m1, layer.attn.wo_b, drop=_od(dr, "wo", a)), h=h2)

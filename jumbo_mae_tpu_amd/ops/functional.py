@@ -217,6 +217,31 @@ def qknorm(qkv: torch.Tensor, hq: Handle, hk: Handle, heads: int, rope=None) -> 
     return _QKNorm.apply(qkv, hq.param, hk.param, hq, hk, heads, rope)
 
 
+# ------------------------------------------------------------------------------- SwiGLU gate
+class _SwiGLU(torch.autograd.Function):
+    """pre [.., 2 Hs] = [gate | up] -> a [.., Hs] = silu(gate) * up with the hidden dropout ``drop`` = (seed,
+    rate) applied inside (ops/swiglu.py); the backward regenerates the mask from the seed."""
+
+    @staticmethod
+    def forward(ctx, pre, drop):
+        p2 = pre.reshape(-1, pre.shape[-1]).contiguous()
+        ctx.save_for_backward(p2)
+        ctx.drop, ctx.shape = drop, pre.shape
+        return P.swiglu_fwd(p2, drop).reshape(*pre.shape[:-1], pre.shape[-1] // 2)
+
+    @staticmethod
+    def backward(ctx, da):
+        (p2,) = ctx.saved_tensors
+        dpre, _ = P.swiglu_bwd(p2, da.reshape(-1, da.shape[-1]).contiguous(), None, ctx.drop)
+        return dpre.reshape(ctx.shape), None
+
+
+def swiglu(pre: torch.Tensor, drop=None) -> torch.Tensor:
+    """The per-op path's gate of the gated feed-forward (the fused blocks call the primitives themselves); the
+    bias gradients of w1 | w3 are the column sums the FF1 Dense's own backward takes of the returned dpre."""
+    return _SwiGLU.apply(pre, drop)
+
+
 # ---------------------------------------------------------------- classification loss + accuracy
 def cls_loss_torch(logits, labels_int, plan=None, smoothing: float = 0.0, criterion: str = "ce"):
     """The torch composition of models/classifier.py on integer labels: scattered one-hot ->

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 from ..models.params import Handle
 from . import _ext
 from . import qknorm as QN
+from . import swiglu as SG
 from .rope import rope_torch
 
 LN_EPS = 1e-6
@@ -168,6 +169,7 @@ _ATTN_STATS_OURS = True  # attention monitor's per-head statistics on the fused 
 _ATTN_MAPS_OURS = True  # attention maps' rollout step on the fused kernels (csrc/attn_rollout.hip), else the torch composition
 _ROPE_OURS = True  # rotary position embedding of q and k on the kernel (csrc/rope.hip), else the torch composition
 _QKNORM_OURS = True  # QK-norm (+ rope) of q and k on the fused kernels (csrc/qknorm.hip), else the torch composition
+_SWIGLU_OURS = True  # the gated feed-forward's gate on the kernels (csrc/swiglu.hip), else the torch composition
 
 
 NARROW_MAX_M = 4096  # csrc/gemm_plan.h GEMM_NARROW_MAX_M: below it the NT GEMMs (split-K too) take 128 x 192 tiles
@@ -543,6 +545,47 @@ def gelu_bwd(h: torch.Tensor, da: torch.Tensor, hb: Handle | None = None,
     t = torch.tanh(u)
     d = 0.5 * (1 + t) + 0.5 * hf * (1 - t * t) * _GELU_C * (1 + 3 * 0.044715 * hf * hf)
     return (da.float() * d).to(h.dtype), False
+
+
+# ------------------------------------------------------------------------------ SwiGLU gate
+def _swiglu_hip(pre: torch.Tensor) -> bool:
+    """bf16 HIP tensors take csrc/swiglu.hip; the CPU, fp32 and ``_SWIGLU_OURS = False`` take the torch
+    composition (ops/swiglu.py), and so does a shape the kernels answer with a negative status."""
+    return _SWIGLU_OURS and hip(pre) and pre.dtype == torch.bfloat16 and pre.dim() == 2 and pre.is_contiguous()
+
+
+def _swiglu_mask(pre: torch.Tensor, drop):
+    """The composition's keep / keep_p factors of ``drop`` = (seed, rate): the kernels' mask, bit for bit."""
+    if drop is None or drop[1] <= 0.0:
+        return None
+    return SG.drop_factors(drop[0], pre.shape[0], pre.shape[1] // 2, drop[1], pre.device)
+
+
+def _wide(t: torch.Tensor) -> torch.Tensor:
+    return t if t.dtype in (torch.float32, torch.float64) else t.float()
+
+
+def swiglu_fwd(pre: torch.Tensor, drop=None) -> torch.Tensor:
+    """a [M, Hs] = silu(gate) * up of pre [M, 2 Hs] = [gate | up] (ops/swiglu.py holds the definition), fp32
+    arithmetic and one rounding.  ``drop`` = (seed int64 [1] tensor, rate): the hidden dropout, its mask
+    indexed by the element of a and regenerated in the backward."""
+    if _swiglu_hip(pre):
+        rc, a = _ext.load().swiglu_fwd(pre, drop[0] if drop else None, drop[1] if drop else 0.0)
+        if rc >= 0:
+            return a
+    return SG.swiglu_torch(_wide(pre), _swiglu_mask(pre, drop)).to(pre.dtype)
+
+
+def swiglu_bwd(pre: torch.Tensor, da: torch.Tensor, hb: Handle | None = None, drop=None) -> tuple[torch.Tensor, bool]:
+    """dpre [M, 2 Hs] of ``swiglu_fwd`` for da [M, Hs]; when ``hb`` (the [2 Hs] handle over b1 | b3) is given
+    its gradient colsum(dpre) is fused in.  Returns (dpre, bias_done)."""
+    if _swiglu_hip(pre):
+        bg = hb.grad if _trainable(hb) else None
+        rc, dpre = _ext.load().swiglu_bwd(pre, da.contiguous(), bg, drop[0] if drop else None,
+                                          drop[1] if drop else 0.0)
+        if rc >= 0:
+            return dpre, bg is not None
+    return SG.swiglu_bwd_torch(_wide(pre), _wide(da), _swiglu_mask(pre, drop)).to(pre.dtype), False
 
 
 # ------------------------------------------------------------------------------ layernorm

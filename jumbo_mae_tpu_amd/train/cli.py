@@ -4,8 +4,8 @@ Reference: /root/reference/src/main_pretrain.py:97-167 and main_finetune.py:97-1
 underscore spelling of ``--image_mask_ratio`` and the seeds defaulting to ``random.randint`` at
 parse time).  Additions (all optional, defaults keep reference behaviour): ``--resume``,
 ``--save-interval``, ``--mask-mode``, ``--compute-dtype``, ``--bucket-mb``, ``--device``,
-``--log-norms``, ``--ema-decay``, the distillation flags ``--teacher-*`` / ``--distill-*`` and
-``--eval-report`` / ``--eval-report-bins`` (``main_finetune`` only).
+``--log-norms``, ``--ffn`` / ``--dec-ffn`` (gelu | swiglu, the feed-forward kind), ``--ema-decay``, the
+distillation flags ``--teacher-*`` / ``--distill-*`` and ``--eval-report`` / ``--eval-report-bins`` (``main_finetune`` only).
 Flags the reference accepts but ignores (``--pooling``, ``--dec-posemb``, ``--label-mapping``,
 ``--ipaddr``, ``--hostname``; quirk Q10) are accepted and recorded.
 """
@@ -55,6 +55,11 @@ def _model(p: argparse.ArgumentParser, posemb: str):
                         "trainable scale each per layer (the remedy for growing attention logits, val/attn_max_logit); "
                         "fused with --posemb rope into one pass.  A checkpoint loads only into a model of the same "
                         "--qk-norm")
+    p.add_argument("--ffn", choices=("gelu", "swiglu"), default="gelu",
+                   help="feed-forward kind of the encoder, its shared jumbo MLP included: gelu = Dense(4 dim) -> gelu -> "
+                        "Dense, swiglu = W2 (silu(W1 x) * (W3 x)) at the parameter-matched hidden width "
+                        "ceil((8 dim / 3) / 128) * 128 (768 -> 2048; no width flag), with the new leaves .../ff/w3.  A "
+                        "checkpoint loads only into a model of the same --ffn")
     p.add_argument("--pooling", default="cls")
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--droppath", type=float, default=0.1)
@@ -168,6 +173,8 @@ def pretrain_parser() -> argparse.ArgumentParser:
     p.add_argument("--dec-posemb", default="sincos2d")
     p.add_argument("--dec-qk-norm", choices=("none", "rms"), default="none",
                    help="--qk-norm for the MAE decoder's attention layers")
+    p.add_argument("--dec-ffn", choices=("gelu", "swiglu"), default="gelu",
+                   help="--ffn for the MAE decoder's blocks")
     p.add_argument("--dec-dropout", type=float, default=0.0)
     p.add_argument("--dec-droppath", type=float, default=0.1)
     p.add_argument("--norm-pix-loss", action="store_true", default=False)
@@ -223,6 +230,8 @@ def finetune_parser() -> argparse.ArgumentParser:
     ext.add_argument("--teacher-dim", type=int, default=None, help="teacher width (default: --dim)")
     ext.add_argument("--teacher-heads", type=int, default=None, help="teacher heads (default: --heads)")
     ext.add_argument("--teacher-layerscale", action="store_true", default=False)
+    ext.add_argument("--teacher-ffn", choices=("gelu", "swiglu"), default=None,
+                     help="teacher feed-forward kind (default: --ffn)")
     ext.add_argument("--distill-alpha", type=_distill_alpha, default=0.5,
                      help="weight of the distillation term, 0 <= alpha <= 1 (0: the loss without a teacher, bit for "
                           "bit; 1: the teacher alone)")

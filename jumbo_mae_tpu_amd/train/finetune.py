@@ -54,7 +54,7 @@ def build_model(args, device, dtype, rank: int = 0) -> FinetuneModel:
     linear = args.mode == "linear"
     vc = ViTConfig(layers=args.layers, dim=args.dim, heads=args.heads, labels=args.labels, layerscale=args.layerscale,
                    patch_size=args.patch_size, image_size=args.image_size, posemb=args.posemb, pooling=args.pooling,
-                   rope_theta=args.rope_theta, qk_norm=args.qk_norm,
+                   rope_theta=args.rope_theta, qk_norm=args.qk_norm, ffn=args.ffn,
                    dropout=args.dropout, droppath=args.droppath, grad_ckpt=args.grad_ckpt, image_mask_ratio=None,
                    linear_probing=linear, batch_norm=linear)
     mix = Mixup(args.mixup, args.cutmix, seed=args.mixup_seed * 1009 + rank)
@@ -63,13 +63,13 @@ def build_model(args, device, dtype, rank: int = 0) -> FinetuneModel:
 
 def build_teacher(args, device, dtype, log=print) -> FinetuneModel:
     """--teacher-ckpt: the frozen distillation teacher -- the student's patch size, image size, labels and
-    position embedding; its own depth / width / heads / layerscale; no BatchNorm head, dropout, droppath
+    position embedding; its own depth / width / heads / layerscale / feed-forward kind; no BatchNorm head, dropout, droppath
     or Mixup -- with EVERY leaf (encoder and head) taken from the checkpoint: a missing leaf or a shape
     mismatch is an error that names the leaf.  Every rank holds the whole teacher (rank 0's copy)."""
     vc = ViTConfig(layers=args.teacher_layers or args.layers, dim=args.teacher_dim or args.dim,
                    heads=args.teacher_heads or args.heads, labels=args.labels, layerscale=args.teacher_layerscale,
                    patch_size=args.patch_size, image_size=args.image_size, posemb=args.posemb, pooling=args.pooling,
-                   rope_theta=args.rope_theta, qk_norm=args.qk_norm,
+                   rope_theta=args.rope_theta, qk_norm=args.qk_norm, ffn=args.teacher_ffn or args.ffn,
                    dropout=0.0, droppath=0.0, grad_ckpt=False, image_mask_ratio=None, linear_probing=False,
                    batch_norm=False)
     teacher = FinetuneModel(vc, None, 0.0, args.criterion).freeze().to(device, dtype, seed=args.init_seed)

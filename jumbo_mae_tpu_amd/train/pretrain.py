@@ -46,11 +46,12 @@ from .meter import AverageMeter, Logger
 def build_model(args, device, dtype) -> PretrainModel:
     vc = ViTConfig(layers=args.layers, dim=args.dim, heads=args.heads, labels=args.labels, layerscale=args.layerscale,
                    patch_size=args.patch_size, image_size=args.image_size, posemb=args.posemb, pooling=args.pooling,
-                   rope_theta=args.rope_theta, qk_norm=args.qk_norm,
+                   rope_theta=args.rope_theta, qk_norm=args.qk_norm, ffn=args.ffn,
                    dropout=args.dropout, droppath=args.droppath, grad_ckpt=args.grad_ckpt,
                    image_mask_ratio=args.image_mask_ratio, linear_probing=False)
     dc = DecoderConfig(dec_layers=args.dec_layers, dec_dim=args.dec_dim, dec_heads=args.dec_heads,
                        dec_layerscale=args.dec_layerscale, dec_posemb=args.dec_posemb, dec_qk_norm=args.dec_qk_norm,
+                       dec_ffn=args.dec_ffn,
                        dec_dropout=args.dec_dropout,
                        dec_droppath=args.dec_droppath, grad_ckpt=args.grad_ckpt, patch_size=args.patch_size,
                        image_size=args.image_size)

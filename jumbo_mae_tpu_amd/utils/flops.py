@@ -13,18 +13,22 @@ from ..config import DecoderConfig, ViTConfig
 MI355X_BF16_DENSE_PEAK = 2.5e15  # FLOP/s per GPU, dense (no 2:4 sparsity)
 
 
-def _block(tokens: int, dim: int, hidden: int, ff_tokens: int) -> float:
+def _ff(tokens: int, dim: int, hidden: int, ffn: str = "gelu") -> float:
+    """Two [dim, hidden] GEMMs for the GELU feed-forward, three (gate, up, down) for the gated one."""
+    return (3 if ffn == "swiglu" else 2) * 2 * tokens * dim * hidden
+
+
+def _block(tokens: int, dim: int, hidden: int, ff_tokens: int, ffn: str = "gelu") -> float:
     qkv_o = 2 * tokens * dim * 4 * dim
     attn = 2 * 2 * tokens * tokens * dim
-    ff = 2 * 2 * ff_tokens * dim * hidden
-    return qkv_o + attn + ff
+    return qkv_o + attn + _ff(ff_tokens, dim, hidden, ffn)
 
 
 def encoder_fwd_flops(vc: ViTConfig, keep: int) -> float:
     c = vc.num_cls_tokens
     t = c + keep
     d = vc.dim
-    per_layer = _block(t, d, vc.hidden_dim, keep) + 2 * 2 * (c * d) * (4 * c * d)  # + shared jumbo MLP
+    per_layer = _block(t, d, vc.hidden_dim, keep, vc.ffn) + _ff(1, c * d, vc.jumbo_hidden_dim, vc.ffn)  # + shared jumbo MLP
     embed = 2 * keep * (vc.patch_size ** 2 * 3) * d
     return vc.layers * per_layer + embed
 
@@ -35,7 +39,7 @@ def pretrain_fwd_flops_per_image(vc: ViTConfig, dc: DecoderConfig) -> float:
     c = vc.num_cls_tokens
     enc = encoder_fwd_flops(vc, keep)
     proj = 2 * (c + keep) * vc.dim * dc.dec_dim
-    dec = dc.dec_layers * _block(c + n, dc.dec_dim, dc.hidden_dim, c + n)
+    dec = dc.dec_layers * _block(c + n, dc.dec_dim, dc.hidden_dim, c + n, dc.dec_ffn)
     pred = 2 * n * dc.dec_dim * (vc.patch_size ** 2 * 3)
     return enc + proj + dec + pred
 
